@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: frames/s of VToonify-D inference at 1024x1024 output on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -20,7 +20,8 @@ demodulation, AdaIN gamma/beta) is recomputed every frame like the reference doe
 For N>1 every rank processes its own shard of frames (weak scaling: per-GPU work fixed);
 the only collective is the one-time RCCL broadcast of weights + style code before the timed
 region (vtoonify_amd/frames.py).  Timing: barrier + synchronize on both sides of exactly K
-steps, MAX over ranks; value = N*K*batch / that time.
+steps, MAX over ranks; value = N*K*batch / that time.  --dump-outputs DIR writes the frames rank 0's last timed step
+returned as DIR/y.npy (float32), so two builds can be compared output for output on the same seeded inputs.
 
 The JSON line also carries
   roofline      the dominant kernel of the frame (largest share of GPU time), its achieved
@@ -434,6 +435,29 @@ def timed_blocks(step, steps, dev, min_seconds=1.0, max_blocks=64):
     return srt[len(srt) // 2], times
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """Write each tensor of `arrays` as out_dir/<name>.npy in float32 (bf16 converts exactly).  When they exceed
+    DUMP_BYTES together, each is replaced by the same share of its flattened elements at indices drawn from a generator
+    seeded with `seed` and sorted: a function of the shape alone, so two runs with the same arguments sample the same
+    elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(4 * t.numel() for t in arrays.values())
+    for name, t in arrays.items():
+        shape, t = tuple(t.shape), t.detach()
+        if total > DUMP_BYTES:
+            k = t.numel() * DUMP_BYTES // total
+            idx = np.sort(np.random.default_rng(seed).integers(0, t.numel(), size=k))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        path = os.path.join(out_dir, f"{name}.npy")
+        np.save(path, t.float().cpu().numpy())
+        print(f"[bench] {name} {shape} -> {path}" + (f" ({t.numel()} sampled elements)" if total > DUMP_BYTES else ""),
+              file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -462,7 +486,11 @@ def main():
                          "extra keys) can run under torch.distributed.run without GPUs.  The JSON line is marked "
                          '"data": "dry-run"')
     ap.add_argument("--min-seconds", type=float, default=1.0,
-                    help="repeat the --steps block until this much timed work has run; value = median block")
+                    help="extra keys only (capped at 0.5 s there): repeat their blocks until this much timed work has run; "
+                         "`value` is always one block of exactly --steps steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step to DIR/<name>.npy (float32, <= 64 MB: a "
+                         "fixed seeded sample of a larger output); same arguments -> same inputs, so two builds compare")
     ap.add_argument("--cpu-budget", type=float, default=25.0, help="seconds of CPU work for cpu_baseline")
     ap.add_argument("--op-iters", type=int, default=5, help="instrumented frames for per-kernel timing")
     ap.add_argument("--kernels", action="store_true", help="also print the per-kernel table (stderr)")
@@ -521,10 +549,14 @@ def main():
     lanes = max(1, args.lanes)
     streams = [torch.cuda.current_stream(dev)] + [torch.cuda.Stream(dev) for _ in range(lanes - 1)]
 
+    last = {}   # the output of the most recent step (a borrowed plan buffer: valid until its lane runs again)
+
     def step(i):
         ln = i % lanes
         with torch.cuda.stream(streams[ln]):
-            return eng.forward(pool[i % len(pool)], style, d_s, shared_style=True, use_graph=use_graph, lane=ln, borrow=True)
+            last["y"] = eng.forward(pool[i % len(pool)], style, d_s, shared_style=True, use_graph=use_graph, lane=ln,
+                                    borrow=True)
+            return last["y"]
 
     for i in range(max(args.warmup, lanes)):
         y = step(i)
@@ -537,7 +569,10 @@ def main():
     checksum = {"mean_abs": float(yf.abs().mean()), "max_abs": float(yf.abs().max()),
                 "samples": [float(v) for v in yf.flatten()[:: max(1, yf.numel() // 8)][:8]]}
 
-    elapsed, blocks = timed_blocks(step, args.steps, dev, args.min_seconds)
+    # exactly --steps timed steps: one block (the extras below repeat theirs up to --min-seconds)
+    elapsed, blocks = timed_blocks(step, args.steps, dev, 0.0)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"y": last["y"]})   # before any later call reuses the lane's buffer
 
     # the headline's lane-0 plan, held from here on: the extras below build more plans than the engine's LRU keeps
     # (ADVICE r3), and the per-kernel pass at the end must time THIS plan, not a rebuilt one

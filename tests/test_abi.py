@@ -3,6 +3,7 @@ symbol declared in include/vtoonify_amd.h; the loader fails loudly when it is mi
 Python op surface has the reference's signatures.  No kernel is launched here."""
 import ctypes
 import inspect
+import json
 import os
 import re
 import sys
@@ -65,11 +66,20 @@ def test_op_surface_signatures_match_reference():
         assert op.conv2d_gradfix.weight_gradients_disabled is True
     m = op.FusedLeakyReLU(7)
     assert list(m.state_dict()) == ["bias"] and m.bias.shape == (7,)
-    # against the reference itself when it is mounted (authoring container only)
-    ref = "/root/reference/model/stylegan/op_cpu/upfirdn2d.py"
-    if os.path.exists(ref):
-        src = open(ref).read()
-        assert "def upfirdn2d(inputs, kernel, up=1, down=1, pad=(0, 0))" in src
+    # against the reference's own signatures (tests/golden/reference_api.json, parsed from its `model.stylegan.op` and
+    # CPU twin `op_cpu` by tests/golden/make_golden_api.py): same names and defaults as op, same positions as op_cpu
+    with open(os.path.join(REPO, "tests", "golden", "reference_api.json")) as f:
+        api = json.load(f)
+    for name, ref in api["op"].items():
+        obj = op
+        for part in name.split("."):
+            obj = getattr(obj, part)
+        params = inspect.signature(obj).parameters
+        mine = {"params": list(params), "defaults": {k: json.loads(json.dumps(p.default)) for k, p in params.items()
+                                                     if p.default is not inspect.Parameter.empty}}
+        assert mine == ref, name
+        twin = api["op_cpu"][name]
+        assert twin["params"][1:] == ref["params"][1:] and twin["defaults"] == ref["defaults"], name
 
 
 def test_vtoonify_signature_and_state_dict_schema():

@@ -33,12 +33,18 @@ def _check(line):
 
 
 @pytest.mark.gpu
-def test_bench_single_process():
+def test_bench_single_process(tmp_path):
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "5", "--warmup", "2",
-                        "--no-cpu-baseline", "--op-iters", "1", "--no-video", "--min-seconds", "0.2"],
+                        "--no-cpu-baseline", "--op-iters", "1", "--no-video", "--min-seconds", "0.2",
+                        "--dump-outputs", str(tmp_path)],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _check(r.stdout.strip().splitlines()[-1])
+    # --steps is the timed step count; the last step's frames (4 x 3x1024x1024 float32 = 48 MB) are written whole
+    assert d["steps"] == 5 and d["timed_blocks"] == 1
+    import numpy as np
+    y = np.load(tmp_path / "y.npy")
+    assert y.dtype == np.float32 and y.shape == (4, 3, 1024, 1024) and np.isfinite(y).all()
     assert d["n_gpus"] == 1 and d["cpu_baseline"] is None or d["n_gpus"] == 1
     # extra keys: the reference's --batch_size 4, config 3's per-rank step, one frame in flight, and the
     # drop-in module's __call__ (hipGraph by default: within 15 % of the engine's single-stream rate here,
@@ -58,6 +64,38 @@ def test_bench_under_torch_distributed_run_one_rank():
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     _check([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
+
+
+def test_bench_dump_outputs_dry_run_emulation(tmp_path):
+    """--dump-outputs DIR (host emulation, one process): DIR/y.npy is the float32 copy of what the LAST of exactly
+    --steps timed steps returned -- the engine's frames for that step's input (step i runs synthetic frame batch i % 4)
+    -- and a second run with the same arguments writes the same bytes."""
+    import numpy as np
+    import torch
+    ys = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--dry-run-emu",
+               "--height", "8", "--width", "8", "--lanes", "2", "--dtype", "bf16", "--backbone", "toonify", "--batch", "2",
+               "--no-extras", "--op-iters", "1", "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500)
+        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+        d = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
+        assert d["steps"] == 3 and d["timed_blocks"] == 1
+        assert sorted(os.listdir(out)) == ["y.npy"]
+        y = np.load(out / "y.npy")
+        assert y.dtype == np.float32 and y.shape == (2, 3, 32, 32) and np.isfinite(y).all()
+        ys.append(y)
+    assert np.array_equal(ys[0], ys[1])
+    from conftest import load_keys
+    from emu import build_emu
+    from vtoonify_amd import _lib, synth
+    from vtoonify_amd.engine import VToonifyEngine
+    _lib.use_library(build_emu.build())
+    eng = VToonifyEngine(synth.synth_state_dict(load_keys("T"), 0), "toonify", 256, torch.bfloat16, torch.device("cpu"))
+    want = [eng.forward(synth.synth_frames(2, 8, 8, seed=i), synth.synth_style(seed=17), 0.5).float().numpy()
+            for i in (1, 2)]
+    assert np.array_equal(ys[0], want[1]) and not np.array_equal(ys[0], want[0])
 
 
 def test_bench_two_ranks_dry_run_gloo_emulation():

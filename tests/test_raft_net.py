@@ -77,14 +77,13 @@ def test_module_surface_like_smooth_parsing_map(dev):
         m(im1[:, :, :-3], im2[:, :, :-3])
 
 
-@pytest.mark.skipif(not __import__("os").path.isdir("/root/reference"), reason="reference checkout not mounted")
-def test_reference_construction_lines_run_on_the_mirror(tmp_path):
-    """smooth_parsing_map.py:91-102 executed verbatim (read from the reference at run time) with
-    `from model.raft.core.raft import RAFT` resolved by the mirror package: argparse -> RAFT(args) ->
-    nn.DataParallel -> load_state_dict of a `module.`-prefixed checkpoint -> .module -> .to(device) -> .eval()."""
+def test_reference_raft_options_and_data_parallel_checkpoint_on_the_mirror(tmp_path):
+    """RAFT through the mirror package (`from model.raft.core.raft import RAFT`): built from a namespace of the reference's
+    RAFT option table (tests/golden/reference_api.json), wrapped in nn.DataParallel, loaded from a checkpoint whose keys
+    carry DataParallel's `module.` prefix, unwrapped, in eval mode -- and it computes the golden flow."""
+    import json
     import os
     import sys
-    import textwrap
     from emu import build_emu
     _lib.use_library(build_emu.build())
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -94,13 +93,18 @@ def test_reference_construction_lines_run_on_the_mirror(tmp_path):
     sd = synth.synth_state_dict(load_keys("raft"), 0)
     ck = tmp_path / "raft-things.pth"
     torch.save({"module." + k: v for k, v in sd.items()}, ck)
-    src = "/root/reference/smooth_parsing_map.py"
-    with open(src) as f:
-        code = textwrap.dedent("".join(f.readlines()[90:102]))
-    ns = {"torch": torch, "argparse": argparse, "RAFT": MirrorRAFT, "device": "cpu",
-          "args": argparse.Namespace(raft_path=str(ck))}
-    exec(compile(code, src, "exec"), ns)
-    m = ns["raft_model"]
+    with open(os.path.join(repo, "tests", "golden", "reference_api.json")) as f:
+        options = json.load(f)["raft_options"]
+    assert options == {"model": [None, None], "small": ["store_true", False], "mixed_precision": ["store_true", False],
+                       "alternate_corr": ["store_true", False]}
+    parser = argparse.ArgumentParser()
+    for dest, (kind, _) in options.items():
+        parser.add_argument("--" + dest, **({"action": kind} if kind else {}))
+    m = torch.nn.DataParallel(MirrorRAFT(parser.parse_args(["--model", str(ck)])))
+    m.load_state_dict(torch.load(ck))
+    m = m.module
+    m.to("cpu")
+    m.eval()
     assert isinstance(m, RAFT) and not m.training
     d, _ = load_golden("raft_net.npz")
     im1, im2 = (torch.from_numpy(d[k][:1].astype(np.float32)) for k in ("b__image1", "b__image2"))

@@ -51,20 +51,13 @@ def test_option_table_is_the_references():
         assert mine[k] == v, k
     opt = cli.parse(["--ckpt", "/x/y/model.pt"])
     assert opt.exstyle_path == "/x/y/exstyle_code.npy"          # style_transfer.py:41-42
-    ref = "/root/reference/style_transfer.py"
-    if os.path.exists(ref):                                      # the table above is the reference's, not a memory of it
-        import ast
-        tree = ast.parse(open(ref).read())
-        found = {}
-        for node in ast.walk(tree):
-            if isinstance(node, ast.Call) and getattr(node.func, "attr", "") == "add_argument":
-                kw = {k.arg: k.value for k in node.keywords}
-                dest = node.args[0].value.lstrip("-")
-                if "action" in kw:
-                    found[dest] = ("store_true", False)
-                else:
-                    found[dest] = (eval(kw["type"].id), ast.literal_eval(kw["default"]))
-        assert found == REFERENCE_OPTIONS
+    # the table above is the reference's, not a memory of it: tests/golden/reference_api.json holds the option table
+    # parsed from its style_transfer.py (tests/golden/make_golden_api.py)
+    import json
+    with open(os.path.join(REPO, "tests", "golden", "reference_api.json")) as f:
+        found = {k: (kind if kind == "store_true" else {"str": str, "int": int, "float": float}[kind], default)
+                 for k, (kind, default) in json.load(f)["style_transfer_options"].items()}
+    assert found == REFERENCE_OPTIONS
 
 
 def _clip(tmp_path, n=5, H=16, W=24, seed=3):
