@@ -108,6 +108,12 @@ int vt_fused_bias_act(void* out, const void* x, const void* bias, const void* re
  * (model/stylegan/model.py:273-286) collapses into four 3x3 polyphase filters.
  * transposed != 0: gather form of F.conv_transpose2d (used by the generic
  * conv2d_gradfix.conv_transpose2d entry point only).
+ *
+ * dtype VT_F16 (the operator surface, vtoonify_amd/op): fp16 activations and weights on
+ * v_mfma_f32_16x16x32_f16, fp32 accumulate; out_dtype VT_F16 (NHWC) or VT_F32.  It runs
+ * the generic tile kernels only (KIND 0 / 2 of vt_conv2d_tile, with split-K); up_fir,
+ * rgb_weight, rgb_only, in_absdiff, stats_part, tile_stats and in_tile_stats are
+ * VT_ERR_UNSUPPORTED with it.
  * --------------------------------------------------------------------------------- */
 typedef struct vt_conv_desc {
     const void* src0;      /* NHWC, dtype `dtype` */
@@ -119,6 +125,12 @@ typedef struct vt_conv_desc {
     const void* weight;    /* [phases*cout][kh*kw][c0+c1], dtype `dtype` */
     int32_t cout;
     int32_t kh, kw, stride, pad, dil;
+    /* Per-axis geometry (F.conv2d / F.conv_transpose2d with (h, w) tuples): stride and dil carry the vertical value in
+     * bits 0..15 and the horizontal one in bits 16..30, 0 there = the same as the vertical one (every value below
+     * 65536 keeps its meaning); pad_w_p1 below carries the horizontal padding.  Then
+     *   acc = sum_{tap,c} in[n, oy*stride_h + ky*dil_h - pad, ox*stride_w + kx*dil_w - pad_w, c] * w[co,tap,c]
+     * and the transposed gather form likewise per axis.  A conv whose axes differ in any of the three runs on the
+     * generic register-staged kernel. */
     int32_t phases;        /* 1 or 4 */
     int32_t transposed;    /* 0 or 1 */
     const float* in_scale; /* optional per-(n, cin) affine prologue (AdaIN):   */
@@ -132,8 +144,8 @@ typedef struct vt_conv_desc {
     void* out;
     int32_t ld_out;        /* NHWC: per-pixel stride in elements; NCHW: ignored */
     int32_t out_layout;    /* VT_OUT_NHWC / VT_OUT_NCHW */
-    int32_t out_dtype;     /* VT_F32 / VT_BF16 (NCHW output is always fp32) */
-    int32_t dtype;         /* VT_F32 / VT_BF16: dtype of src*, weight; VT_F32X3: fp32 tensors, bf16 x 3 products (above) */
+    int32_t out_dtype;     /* VT_F32 / VT_BF16; VT_F32 / VT_F16 when dtype is VT_F16 (NCHW output is always fp32) */
+    int32_t dtype;         /* VT_F32 / VT_BF16 / VT_F16: dtype of src*, weight; VT_F32X3: fp32 tensors, bf16 x 3 products (above) */
     int32_t tile_hint;     /* 0 = auto; otherwise SPLITK*1000000 + BM*1000 + BN of a compiled tile
                               (SPLITK 0 = auto); +1000000000 forces the register-staged
                               loader where the direct-to-LDS one would apply */
@@ -227,6 +239,7 @@ int vt_conv2d_splitk_mode(const vt_conv_desc* desc);
 
 /* Plain conv weight (cout, cin_src, kh, kw) fp32 -> packed [cout][kh*kw][cin_dst],
  * multiplied by `scale` (EqualConv2d's 1/sqrt(fan_in), model/stylegan/model.py:101,117).
+ * out_dtype: VT_F32, VT_BF16 or VT_F16 (round to nearest even).
  * chan_map[cin_dst] (device int32) gives the source channel of each packed channel, -1
  * for zero padding; NULL = identity.  src_transposed: source is (cin_src, cout, kh, kw)
  * as F.conv_transpose2d expects; spatial taps are flipped for the gather form. */
@@ -456,14 +469,15 @@ int vt_gru_blend(void* h, int ld_h, const void* z, const void* q, int64_t rows, 
 int vt_coords_from_flow(float* coords, const float* flow, int n, int h, int w, vt_stream stream);
 int vt_convex_upsample(float* out, const float* flow, const float* mask, int n, int h, int w, vt_stream stream);
 
-/* Layout converters at the boundary (frames arrive NCHW fp32, model/vtoonify.py:210). */
+/* Layout converters at the boundary (frames arrive NCHW fp32, model/vtoonify.py:210).
+ * in_dtype / out_dtype: VT_F32, VT_BF16 or VT_F16 (exact widening, round-to-nearest-even narrowing). */
 int vt_nchw_to_nhwc(void* out, int ld_out, const void* in, int n, int c, int hw,
                     int in_dtype, int out_dtype, vt_stream stream);
 int vt_nhwc_to_nchw(void* out, const void* in, int ld_in, int n, int c, int hw,
                     int in_dtype, int out_dtype, vt_stream stream);
 
 /* MFMA fragment-layout self test: C = A(16xK) * B(KxN)^T on one wavefront, used by the
- * GPU test-suite to pin the 16x16x32 bf16 / 16x16x4 f32 lane maps on real hardware. */
+ * GPU test-suite to pin the 16x16x32 bf16 / f16 and 16x16x4 f32 lane maps on real hardware. */
 int vt_mfma_selftest(float* c, const void* a, const void* b, int dtype, vt_stream stream);
 
 #ifdef __cplusplus

@@ -456,7 +456,7 @@ template <typename T>
 static bool fullk_eligible(const ConvArgs& a, const void* wstream, FullkArgs& g) {
     constexpr int ESZ = (int)sizeof(T);
     constexpr int BK = 8 * (16 / ESZ);
-    if (!wstream || a.force_generic || a.transposed || a.in_scale || a.rgb_w) return false;
+    if (!wstream || a.force_generic || !axes_equal(a) || a.transposed || a.in_scale || a.rgb_w) return false;
     if (a.taps != 9 || a.kw != 3 || a.stride != 1 || a.pad != a.dil || a.dil < 1 || a.dil > 8) return false;
     if (a.Ho != a.H || a.Wo != a.W || a.phases != 1) return false;
     if (a.cin % (FK_NW * BK) != 0 || a.c0 % BK != 0 || a.coutT % 8 != 0) return false;

@@ -28,6 +28,7 @@
 // pixel-shuffle for the polyphase up-sampling conv, NHWC or planar NCHW stores) runs
 // from an LDS-staged fp32 tile so every global store is a full 16-byte vector.
 #include <stdlib.h>
+#include <type_traits>
 #include <utility>
 
 #include "vt_common.hpp"
@@ -39,6 +40,7 @@ typedef emu_f32x4 f32x4;
 #else
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 #endif
 
 // fp32 slab row length: whole 32-channel fragment groups, so that fragment-order columns stay in the row
@@ -89,7 +91,12 @@ struct ConvArgs {
     int in_absdiff;             // vt_conv_desc.in_absdiff: input = cat[src0, |src0 - src1|] (thin kernel)
     int x3;             // vt_conv_desc.dtype == VT_F32X3: fp32 tensors, products as three bf16 MFMAs where the instance exists
     int blk_pm, blk_cn;  // decode_block_2d: pixel tiles x channel tiles of the block of tiles one XCD owns (0 = channel-major order)
+    int stride_x, dil_x;  // horizontal stride / dilation (high halves of vt_conv_desc.stride / dil); stride / dil: vertical
 };
+
+// One geometry on both axes: the only form the specialised kernel families are written for.  Anything else runs the generic
+// register-staged kernel (force_generic), and every family's eligibility check refuses it as well.
+static inline bool axes_equal(const ConvArgs& a) { return a.stride_x == a.stride && a.dil_x == a.dil && a.pad_x == a.pad; }
 
 template <typename T>
 struct Mma;
@@ -104,6 +111,40 @@ struct Mma<bf16_t> {
 #else
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a),
                                                       __builtin_bit_cast(bf16x8_t, b), acc, 0, 0, 0);
+#endif
+    }
+};
+#ifdef VT_EMU
+// v_mfma_f32_16x16x32_f16: the lane map of the bf16 form (lane l holds A[l&15][8*(l>>4)+j], B[8*(l>>4)+j][l&15]), fp16 operands
+static inline emu_f32x4 emu_mfma_f32_16x16x32_f16(const u128& a, const u128& b, emu_f32x4 c) {
+    struct Frag {
+        uint16_t a[8], b[8];
+    } mine;
+    memcpy(mine.a, &a, 16);
+    memcpy(mine.b, &b, 16);
+    const unsigned char* all = emu::exchange(&mine, sizeof(Frag));
+    const int lane = emu::cur()->lane;
+    const int col = lane & 15;
+    emu_f32x4 d = c;
+    for (int r = 0; r < 4; ++r) {
+        const int row = 4 * (lane >> 4) + r;
+        float acc = d[r];
+        for (int q = 0; q < 4; ++q)
+            for (int j = 0; j < 8; ++j)
+                acc += emu_half_to_float(emu::lane_frag<Frag>(all, row + 16 * q).a[j]) *
+                       emu_half_to_float(emu::lane_frag<Frag>(all, col + 16 * q).b[j]);
+        d[r] = acc;
+    }
+    return d;
+}
+#endif
+template <>
+struct Mma<f16_t> {   // same fragment layout and cycles as the bf16 form (8 consecutive k per lane)
+    static __device__ __forceinline__ void run(f32x4& acc, const u128& a, const u128& b) {
+#ifdef VT_EMU
+        acc = emu_mfma_f32_16x16x32_f16(a, b, acc);
+#else
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), acc, 0, 0, 0);
 #endif
     }
 };
@@ -164,6 +205,26 @@ struct Mma<f32x3_t> {   // on already split operands: (weights head, weights rem
         Mma<bf16_t>::run(acc, wl, ah);
     }
 };
+// bf16 operands: the compute type the specialised kernel families are written for (they pack to bf16 or run bf16 MFMAs inside).
+// fp16 has the generic tile kernels only (ConvArgs of the operator surface, dispatch_generic).
+template <typename T>
+struct is_bf16 {
+    static constexpr bool value = false;
+};
+template <>
+struct is_bf16<bf16_t> {
+    static constexpr bool value = true;
+};
+// 16-bit element type of a conv output that is not fp32 (!out_f32): fp16 for fp16 operands, bf16 for every other compute type
+template <typename T>
+struct Out16 {
+    using type = bf16_t;
+};
+template <>
+struct Out16<f16_t> {
+    using type = f16_t;
+};
+
 // One 128-byte K row of a wave tile: acc[a][b] += W_b . A_a over the row's channels.  `pa(a, sub)` / `pb(b, sub)` give
 // the LDS address of the 16-byte chunk (sub * 4 + q) of pixel fragment a / weight fragment b.  bf16 / fp32: the two
 // half-row steps of the kernels' original loops, verbatim; f32x3: both halves, split, three products.
@@ -218,7 +279,8 @@ __device__ __forceinline__ void post_act_n(const ConvArgs& p, float* f) {
 }
 
 // Finished values (bias/activation/gain applied) of 8 consecutive output columns n..n+7 of
-// GEMM row m -> NHWC store with the optional residual add and the polyphase pixel shuffle.
+// GEMM row m -> NHWC store with the optional residual add and the polyphase pixel shuffle.  OT: the 16-bit output type.
+template <typename OT = bf16_t>
 __device__ __forceinline__ void store_nhwc8(const ConvArgs& p, int m, int n, float* f) {
     const int HoWo = p.Ho * p.Wo;
     int64_t opix = m;
@@ -251,20 +313,20 @@ __device__ __forceinline__ void store_nhwc8(const ConvArgs& p, int m, int n, flo
             for (int i = 0; i < nvalid; ++i) o[i] = post_act(p, f[i] + (rs ? p.beta * rs[i] : 0.0f));
         }
     } else {
-        bf16_t* o = (bf16_t*)p.out + opix * p.ld_out + co;
-        const bf16_t* rs = p.resid ? (const bf16_t*)p.resid + opix * p.ld_res + co : nullptr;
+        OT* o = (OT*)p.out + opix * p.ld_out + co;
+        const OT* rs = p.resid ? (const OT*)p.resid + opix * p.ld_res + co : nullptr;
         if (p.vec_store && nvalid == 8) {
             if (rs) {
                 float g[8];
-                unpack16<bf16_t>(ld128(rs), g);
+                unpack16<OT>(ld128(rs), g);
 #pragma unroll
                 for (int i = 0; i < 8; ++i) f[i] += p.beta * g[i];
             }
             post_act_n<8>(p, f);
-            st128(o, pack16<bf16_t>(f));
+            st128(o, pack16<OT>(f));
         } else {
             for (int i = 0; i < nvalid; ++i)
-                o[i] = from_f32<bf16_t>(post_act(p, f[i] + (rs ? p.beta * to_f32(rs[i]) : 0.0f)));
+                o[i] = from_f32<OT>(post_act(p, f[i] + (rs ? p.beta * to_f32(rs[i]) : 0.0f)));
         }
     }
 }
@@ -356,7 +418,8 @@ struct PatchRows {    // 2-D tiles of TW-pixel rows (patch-resident kernel)
 };
 
 // Four consecutive output columns n..n+3 of GEMM row m, finished (bias/activation/gain applied):
-// residual add, pixel shuffle of the polyphase form, NHWC (8/16-byte store) or planar NCHW.
+// residual add, pixel shuffle of the polyphase form, NHWC (8/16-byte store) or planar NCHW.  OT: the 16-bit output type.
+template <typename OT = bf16_t>
 __device__ __forceinline__ void store_out4(const ConvArgs& p, int m, int n, float* f) {
     const int HoWo = p.Ho * p.Wo;
     if (p.out_layout == VT_OUT_NHWC) {
@@ -389,6 +452,12 @@ __device__ __forceinline__ void store_out4(const ConvArgs& p, int m, int n, floa
                 for (int i = 0; i < 4; ++i)
                     if (i < nvalid) o[i] = post_act(p, f[i] + (rs ? p.beta * rs[i] : 0.0f));
             }
+        } else if constexpr (!is_bf16<OT>::value) {
+            OT* o = (OT*)p.out + opix * p.ld_out + co;
+            const OT* rs = p.resid ? (const OT*)p.resid + opix * p.ld_res + co : nullptr;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (i < nvalid) o[i] = from_f32<OT>(post_act(p, f[i] + (rs ? p.beta * to_f32(rs[i]) : 0.0f)));
         } else {
             bf16_t* o = (bf16_t*)p.out + opix * p.ld_out + co;
             const bf16_t* rs = p.resid ? (const bf16_t*)p.resid + opix * p.ld_res + co : nullptr;
@@ -445,7 +514,8 @@ __device__ __forceinline__ int frag_channel(int b, int q) {  // first of the 4 c
     return (b >> 1) * 32 + q * 8 + (b & 1) * 4;
 }
 
-// Eight consecutive output columns n..n+7 of GEMM row m (bf16 NHWC, vector path): one 16-byte store.
+// Eight consecutive output columns n..n+7 of GEMM row m (16-bit NHWC of type OT, vector path): one 16-byte store.
+template <typename OT = bf16_t>
 __device__ __forceinline__ bool store_out8_bf16(const ConvArgs& p, int m, int n, float* f, bool have_rpre = false,
                                                 u128 rpre = u128{0u, 0u, 0u, 0u}) {
     // rpre (have_rpre): the residual vector of this store, fetched by the caller ahead of ALL its stores
@@ -463,15 +533,15 @@ __device__ __forceinline__ bool store_out8_bf16(const ConvArgs& p, int m, int n,
     }
     const int lim = (p.phases > 1) ? p.cout : p.coutT;
     if (co + 8 > lim || ((p.ld_out | co) & 7) || (p.resid && (p.ld_res & 7))) return false;
-    bf16_t* o = (bf16_t*)p.out + opix * p.ld_out + co;
+    OT* o = (OT*)p.out + opix * p.ld_out + co;
     if (p.resid) {
         float g[8];
-        unpack16<bf16_t>(have_rpre ? rpre : ld128((const bf16_t*)p.resid + opix * p.ld_res + co), g);
+        unpack16<OT>(have_rpre ? rpre : ld128((const OT*)p.resid + opix * p.ld_res + co), g);
 #pragma unroll
         for (int i = 0; i < 8; ++i) f[i] += p.beta * g[i];
     }
     post_act_n<8>(p, f);
-    st128(o, pack16<bf16_t>(f));
+    st128(o, pack16<OT>(f));
     return true;
 }
 
@@ -568,6 +638,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x4 (&acc)[BM
     // the registers, else by the overload below right here
     constexpr int TM = BM / WM / 16, TN = BN / WN / 16;
     constexpr bool PERM = (TN % 2 == 0);
+    using OT = typename Out16<T>::type;   // 16-bit output type (!out_f32)
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
@@ -667,7 +738,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x4 (&acc)[BM
             for (int a = 0; a < TM; ++a) {
                 const int m = rowmap(wm * (TM * 16) + a * 16 + l15);
                 const bool ok = m >= 0 && nn + 8 <= p.coutT;
-                rpre[b0 / BS][a] = ld128((const bf16_t*)p.resid + (int64_t)(ok ? m : 0) * p.ld_res + (ok ? nn : 0));
+                rpre[b0 / BS][a] = ld128((const OT*)p.resid + (int64_t)(ok ? m : 0) * p.ld_res + (ok ? nn : 0));
             }
         }
     }
@@ -679,7 +750,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x4 (&acc)[BM
     // its table loads nor its stores.
     bool lean = false;
     if constexpr (BS == 2) {
-        constexpr bool H = sizeof(T) == 2;   // bf16 rows (one 16-byte store per 8 channels) or fp32 rows (two)
+        constexpr bool H = sizeof(T) == 2;   // 16-bit rows of type OT (one 16-byte store per 8 channels) or fp32 rows (two)
         lean = EPI == 1 ||   // (the same predicate on the host: conv_lean())
                ((p.act == VT_ACT_NONE || p.act == VT_ACT_LRELU) && p.phases == 1 && p.out_layout == VT_OUT_NHWC &&
                 (H ? !p.out_f32 : p.out_f32 != 0) && p.vec_store && !p.post_relu && !(p.coutT & 7) &&
@@ -702,7 +773,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x4 (&acc)[BM
             // The weight operand of fragment row a carries its three rows at 4a .. 4a + 2, so the products of the TM <= 4
             // fragment rows land in DIFFERENT rows of one accumulator: lane (q, l15) ends up with the three plane values of
             // pixel l15 of fragment row q -- the reduce-scatter the vector form needed 9 shuffles per plane triple for.
-            constexpr bool RGB_MMA = sizeof(T) == 2;
+            constexpr bool RGB_MMA = is_bf16<T>::value;
             static_assert(!RGB_MMA || TM <= 4, "four fragment rows share the 16 rows of the ToRGB accumulator");
             f32x4 racc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -755,11 +826,11 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x4 (&acc)[BM
                     if constexpr (H) {
                         if (rvec) {
                             float g[8];
-                            unpack16<bf16_t>(rpre[b0 / 2][a], g);
+                            unpack16<OT>(rpre[b0 / 2][a], g);
 #pragma unroll
                             for (int k = 0; k < 8; ++k) f[k] += p.beta * g[k];
                         }
-                        if (live) st128((bf16_t*)p.out + (int64_t)m * p.ld_out + nn, pack16<bf16_t>(f));
+                        if (live) st128((OT*)p.out + (int64_t)m * p.ld_out + nn, pack16<OT>(f));
                     } else {
                         if (p.resid) {   // (fp32: the residual of a pixel is fetched here, at a clamped address)
                             const float* rs = (const float*)p.resid + (int64_t)(live ? m : 0) * p.ld_res + (live ? nn : 0);
@@ -858,10 +929,10 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x4 (&acc)[BM
                         rp[a][j] += (fr[0] * wr[h][j][0] + fr[1] * wr[h][j][1]) + (fr[2] * wr[h][j][2] + fr[3] * wr[h][j][3]);
                 }
             }
-            if (BS == 2 && nh[1] < p.coutT && store_out8_bf16(p, m, nh[0], f, rvec, rpre[b0 / BS][a])) continue;
+            if (BS == 2 && nh[1] < p.coutT && store_out8_bf16<OT>(p, m, nh[0], f, rvec, rpre[b0 / BS][a])) continue;
 #pragma unroll
             for (int h = 0; h < BS; ++h)
-                if (nh[h] < p.coutT) store_out4(p, m, nh[h], f + 4 * h);
+                if (nh[h] < p.coutT) store_out4<OT>(p, m, nh[h], f + 4 * h);
         }
     }
     }   // !lean
@@ -987,7 +1058,7 @@ conv_igemm_kernel(const ConvArgs p) {
         a_img[i] = img;
         a_pix[i] = img * p.H * p.W;
         a_y[i] = p.transposed ? oy + p.pad : oy * p.stride - p.pad;
-        a_x[i] = p.transposed ? ox + p.pad : ox * p.stride - p.pad_x;
+        a_x[i] = p.transposed ? ox + p.pad_x : ox * p.stride_x - p.pad_x;
     }
     const int nk_all = (p.K + BK - 1) / BK;
     const int kt0 = split * p.kps;
@@ -1003,7 +1074,7 @@ conv_igemm_kernel(const ConvArgs p) {
     auto load_tiles = [&]() {
         const bool tap_ok = tap < p.taps;
         const int ky = tap / p.kw, kx = tap - ky * p.kw;
-        const int dy = ky * p.dil, dx = kx * p.dil;
+        const int dy = ky * p.dil, dx = kx * p.dil_x;
         const T* sp;
         int ld, cc;
         if (kc < p.c0) {
@@ -1023,9 +1094,9 @@ conv_igemm_kernel(const ConvArgs p) {
                     in = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
                 } else {
                     const int ty = a_y[i] - dy, tx = a_x[i] - dx;
-                    in = ty >= 0 && tx >= 0 && (ty % p.stride) == 0 && (tx % p.stride) == 0;
+                    in = ty >= 0 && tx >= 0 && (ty % p.stride) == 0 && (tx % p.stride_x) == 0;
                     iy = ty / p.stride;
-                    ix = tx / p.stride;
+                    ix = tx / p.stride_x;
                     in = in && iy < p.H && ix < p.W;
                 }
                 if (in) {
@@ -1746,7 +1817,8 @@ __device__ __forceinline__ int slab_col4(const ConvArgs& p, int n) {
 
 // Second pass of a split-K convolution: sum the K-slices in slice order (deterministic),
 // then the same bias / activation / gain / residual / layout epilogue as the fused kernel.
-// One thread per (GEMM row, 8 output columns).
+// One thread per (GEMM row, 8 output columns).  OT: the 16-bit output type.
+template <typename OT>
 __global__ void __launch_bounds__(256) conv_splitk_reduce_kernel(const ConvArgs p) {
     const int nv = p.ldp / 8;
     const int64_t total = (int64_t)p.M * nv;
@@ -1815,7 +1887,7 @@ __global__ void __launch_bounds__(256) conv_splitk_reduce_kernel(const ConvArgs 
             }
         }
         if (p.out_layout == VT_OUT_NHWC) {
-            store_nhwc8(p, m, n, f);
+            store_nhwc8<OT>(p, m, n, f);
         } else {
             float* o = (float*)p.out;
             const float* rs = (const float*)p.resid;
@@ -1952,19 +2024,22 @@ static bool stats_fusable(const ConvArgs& a, int esz) {
 // second pass of the two-pass split-K
 template <typename T>
 static int launch_reduce(const ConvArgs& args, vt_stream stream) {
-    if (stats_fusable(args, (int)sizeof(T))) {
-        const int hw = args.Ho * args.Wo;
-        const int cpx = stat_chunk_pixels(hw);
-        const int chunks = (hw + cpx - 1) / cpx;
-        const int cgroups = vt_cdiv(args.coutT / (16 / (int)sizeof(T)), 16);
-        auto k = conv_splitk_reduce_stats_kernel<T>;
-        VT_LAUNCH(k, dim3((unsigned)(args.N * chunks * cgroups)), dim3(256), stream, args, cpx, chunks, cgroups);
-        g_stats_emitted = true;
-        return vt_check_launch("vt_conv2d(split-K reduce + statistics)");
+    if constexpr (!std::is_same<T, f16_t>::value) {   // (fp16 convs emit no statistics: fill_args)
+        if (stats_fusable(args, (int)sizeof(T))) {
+            const int hw = args.Ho * args.Wo;
+            const int cpx = stat_chunk_pixels(hw);
+            const int chunks = (hw + cpx - 1) / cpx;
+            const int cgroups = vt_cdiv(args.coutT / (16 / (int)sizeof(T)), 16);
+            auto k = conv_splitk_reduce_stats_kernel<T>;
+            VT_LAUNCH(k, dim3((unsigned)(args.N * chunks * cgroups)), dim3(256), stream, args, cpx, chunks, cgroups);
+            g_stats_emitted = true;
+            return vt_check_launch("vt_conv2d(split-K reduce + statistics)");
+        }
     }
     int64_t blocks = ((int64_t)args.M * (args.ldp / 8) + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    VT_LAUNCH(conv_splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), stream, args);
+    auto kr = conv_splitk_reduce_kernel<typename Out16<T>::type>;
+    VT_LAUNCH(kr, dim3((unsigned)blocks), dim3(256), stream, args);
     return vt_check_launch("vt_conv2d(split-K reduce)");
 }
 
@@ -1974,7 +2049,7 @@ template <typename T>
 static bool glds_eligible(const ConvArgs& a, GldsArgs& g) {
     constexpr int ESZ = (int)sizeof(T);
     constexpr int BK = 8 * (16 / ESZ);
-    if (a.force_generic || a.transposed || a.in_scale) return false;
+    if (a.force_generic || !axes_equal(a) || a.transposed || a.in_scale) return false;
     if (a.c0 % BK != 0 || a.c1 % BK != 0) return false;
     const int64_t lim = ((int64_t)1 << 31) - 4096;
     const int64_t px = (int64_t)a.N * a.H * a.W;
@@ -2093,7 +2168,7 @@ template <typename T>
 static bool patch_eligible(const ConvArgs& a, GldsArgs& g) {
     constexpr int ESZ = (int)sizeof(T);
     constexpr int BK = 8 * (16 / ESZ);
-    if (a.force_generic || a.transposed || a.in_scale) return false;
+    if (a.force_generic || !axes_equal(a) || a.transposed || a.in_scale) return false;
     if (a.taps != 9 || a.kw != 3 || a.stride != 1 || a.pad != a.dil) return false;
     if (a.dil != 1 && a.dil != 2 && a.dil != 4) return false;
     if (a.Ho != a.H || a.Wo != a.W) return false;
@@ -2114,7 +2189,7 @@ template <typename T>
 static bool up_eligible(const ConvArgs& a, GldsArgs& g) {
     constexpr int ESZ = (int)sizeof(T);
     constexpr int BK = 8 * (16 / ESZ);
-    if (a.force_generic || !a.transposed || a.in_scale || a.rgb_w || a.stats_part || a.tile_stats || a.in_tile_stats) return false;
+    if (a.force_generic || !axes_equal(a) || !a.transposed || a.in_scale || a.rgb_w || a.stats_part || a.tile_stats || a.in_tile_stats) return false;
     if (a.taps != 9 || a.kw != 3 || a.stride != 2 || a.pad != 0 || a.pad_x != 0 || a.dil != 1 || a.phases != 1) return false;
     if (a.Ho != 2 * a.H + 1 || a.Wo != 2 * a.W + 1 || a.c1 != 0 || a.c0 % BK != 0 || a.coutT % 8 != 0) return false;
     if (a.out_layout != VT_OUT_NHWC) return false;
@@ -2130,7 +2205,7 @@ static bool up_eligible(const ConvArgs& a, GldsArgs& g) {
 
 template <typename T>
 static bool c32_eligible(const ConvArgs& a, GldsArgs& g) {
-    if (sizeof(T) != 2 || a.force_generic || a.transposed || a.in_scale) return false;
+    if (!is_bf16<T>::value || a.force_generic || !axes_equal(a) || a.transposed || a.in_scale) return false;
     if (a.taps != 9 || a.kw != 3 || a.stride != 1 || a.pad != 1 || a.dil != 1) return false;
     if (a.c0 != 32 || a.c1 != 0 || a.cout % 32 != 0 || a.cout > 256 || a.phases != 1 || a.Ho != a.H || a.Wo != a.W) return false;
     if (a.cout != 32 && (a.rgb_w || a.rgb_only)) return false;   // the fused ToRGB needs all channels in one workgroup
@@ -2176,11 +2251,13 @@ template <typename T>
 static TilePlan choose_plan(const ConvArgs& a, int hint, int64_t ws_floats_avail) {
     constexpr int BK = 8 * (16 / (int)sizeof(T));
     constexpr int wg_target = 256;   // workgroups a split-K launch aims for: one per CU
+    // fp16: the generic 1-D tile kernels only (register-staged / direct-to-LDS, split-K); every specialised family is bf16 / fp32
+    constexpr bool FAM = !std::is_same<T, f16_t>::value;
     TilePlan t;
     t.kind = 0;
     t.bm = t.bn = 0;
     t.splitk = 0;
-    if (a.up_fir) {   // conv_transpose2d + blur: its own kernel family; 16-channel tiles when 32 would leave CUs idle
+    if (FAM && a.up_fir) {   // conv_transpose2d + blur: its own kernel family; 16-channel tiles when 32 would leave CUs idle
         t.kind = 5;
         t.bm = 20 * 28;
         const int64_t tiles = (int64_t)vt_cdiv(2 * a.H, 20) * vt_cdiv(2 * a.W, 28);
@@ -2197,7 +2274,7 @@ static TilePlan choose_plan(const ConvArgs& a, int hint, int64_t ws_floats_avail
         // conv_transpose2d(3x3, stride 2) with wide channels: by output parity on the pipelined patch tiles
         // (256 quads x 64 channels x 4 parity classes per workgroup); anything else transposed: the gather form below
         GldsArgs gu;
-        if (hp != 2 && hbm == 0 && hs == 0 && a.coutT >= 64 && a.cin >= 128 && up_eligible<T>(a, gu)) {
+        if (FAM && hp != 2 && hbm == 0 && hs == 0 && a.coutT >= 64 && a.cin >= 128 && up_eligible<T>(a, gu)) {
             t.kind = 1;
             t.bm = 256, t.bn = 64;
             t.splitk = 1;
@@ -2206,7 +2283,7 @@ static TilePlan choose_plan(const ConvArgs& a, int hint, int64_t ws_floats_avail
     }
     {
         // thin outputs (cout <= 3, planar): one launch, K over the wavefronts of a workgroup, no slabs
-        if ((hp == 6 || (hp == 0 && hbm == 0 && hs == 0)) && thin_eligible<T>(a)) {
+        if (FAM && (hp == 6 || (hp == 0 && hbm == 0 && hs == 0)) && thin_eligible<T>(a)) {
             t.kind = 6;
             t.bm = thin16_wanted(a) ? TH16 * TH16 : TH_TW * TH_TW;   // (16 x 16-pixel tiles at the large levels, conv_thin.hpp)
             t.bn = a.taps * a.coutT > 16 ? 32 : 16;
@@ -2220,7 +2297,7 @@ static TilePlan choose_plan(const ConvArgs& a, int hint, int64_t ws_floats_avail
         return (int64_t)vt_cdiv(a.Ho, th) * vt_cdiv(a.Wo, 16) * vt_cdiv(a.coutT, n);
     };
     GldsArgs g;
-    if constexpr (sizeof(T) == 2) {
+    if constexpr (is_bf16<T>::value) {
         // stride-2 3x3 convs (the encoder's down-sampling convs) by input parity on patch-resident tiles (conv_patch_s2.hpp):
         // from 128 tiles up -- per IMAGE under VT_BATCH_EXACT (its K order is not the 1-D kernel's, so the choice must then not
         // look at the batch), per launch otherwise (like the other batch-aware plans, section 4.1h of DESIGN.md): the 64^2 ->
@@ -2236,7 +2313,7 @@ static TilePlan choose_plan(const ConvArgs& a, int hint, int64_t ws_floats_avail
             return t;
         }
     }
-    if (hp != 2 && hbm == 0 && c32_eligible<T>(a, g)) {   // the 1024^2 level: persistent register-weight kernel
+    if (FAM && hp != 2 && hbm == 0 && c32_eligible<T>(a, g)) {   // the 1024^2 level: persistent register-weight kernel
         t.kind = 3;
         t.bm = 256;
         t.bn = 32;
@@ -2248,7 +2325,7 @@ static TilePlan choose_plan(const ConvArgs& a, int hint, int64_t ws_floats_avail
         // few pixels per image, wide channels.  Per-image geometry only (batch-invariant like every plan).
         FullkArgs fg;
         const bool hinted = hp == 4;
-        if (hp != 2 && (hbm == 0 || hinted) && fullk_eligible<T>(a, a.wstream, fg)) {
+        if (FAM && hp != 2 && (hbm == 0 || hinted) && fullk_eligible<T>(a, a.wstream, fg)) {
             const int64_t wgs = (int64_t)a.dil * a.dil * fg.tiles_y * fg.tiles_x * vt_cdiv(a.coutT, FK_BN);   // per image
             constexpr int fk_max_wgs = 1024;   // largest per-image grid the heuristic gives the whole-K kernel
             // A batch that fills the GPU with 256-pixel x 128-channel patch tiles (one 8-wave workgroup per CU, no K split) is
@@ -2279,7 +2356,7 @@ static TilePlan choose_plan(const ConvArgs& a, int hint, int64_t ws_floats_avail
             // (round 6: dilation 4 on flat 8 x 8 blocks of its 16 sub-images was built and measured -- 30.3 us against the 29.1 of the
             // weight-stationary kernel, same box, profiles/r06_ab_flat8_c32.txt -- and removed: DESIGN.md 4.1u)
             const bool dil_ok = a.dil == 1 || (a.dil == 2 && !(ppe && ppe[0] == '0') && !a.x3);
-            const bool batch_patch32 = sizeof(T) == 2 && !hinted && hbm == 0 && hp == 0 && a.N > 1 && dil_ok && m1 <= 2304 &&
+            const bool batch_patch32 = is_bf16<T>::value && !hinted && hbm == 0 && hp == 0 && a.N > 1 && dil_ok && m1 <= 2304 &&
                                        a.coutT >= 128 && !a.tile_stats && !a.in_tile_stats && !a.stats_part &&
                                        (int64_t)a.N * ptiles(16, 32) >= 256 && !batch_exact() && patch_eligible<T>(a, g);
             if (batch_patch32) {
@@ -2313,7 +2390,7 @@ static TilePlan choose_plan(const ConvArgs& a, int hint, int64_t ws_floats_avail
             }
         }
     }
-    const bool can_patch = hp != 2 && hp != 4 && patch_eligible<T>(a, g);
+    const bool can_patch = FAM && hp != 2 && hp != 4 && patch_eligible<T>(a, g);
     int units = 0;  // K units that can be split: K-steps (1-D) or channel chunks (patch)
     if (hbm > 0 && hp != 4) {
         t.kind = hp == 1 ? 1 : 0;
@@ -2450,7 +2527,7 @@ int launch_patch(const ConvArgs& a, const GldsArgs& g, vt_stream stream) {
 // carry nothing else
 template <typename T>
 static bool conv_lean(const ConvArgs& a) {
-    constexpr bool H = sizeof(T) == 2;
+    constexpr bool H = is_bf16<T>::value;
     return (a.act == VT_ACT_NONE || a.act == VT_ACT_LRELU) && a.phases == 1 && a.out_layout == VT_OUT_NHWC &&
            (H ? !a.out_f32 : a.out_f32 != 0) && a.vec_store && !a.post_relu && !(a.coutT & 7) &&
            (H ? (!a.resid || !(a.ld_res & 7)) && !(a.ld_out & 7) : !(a.ld_out & 3) && (!a.resid || !(a.ld_res & 3)));
@@ -2606,7 +2683,7 @@ int launch_c32(const ConvArgs& a, const GldsArgs& g, vt_stream stream) {
 template <typename T>
 int dispatch(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) {
     ConvArgs a = a0;
-    a.force_generic = hint >= 1000000000 || a.pad_x != a.pad;
+    a.force_generic = hint >= 1000000000 || !axes_equal(a);
     const TilePlan t = choose_plan<T>(a, hint % 1000000000, ws_floats);
     a.splitk = t.splitk;
     a.ldp = slab_ld(a.coutT);
@@ -2636,7 +2713,7 @@ int dispatch(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) 
         const bool db = de ? chunks >= atoi(de) : (chunks >= 4 && (t.bn == 16 || wgs_all <= 768));
         // (single-stage 32-channel forms are capped at 256 registers -- 2 workgroups per CU, a few cold values spilled: 40 vs
         // 51 us and 54 vs 77 us on the 256^2 / 512^2-pixel levels)
-        if constexpr (sizeof(T) == 2) {
+        if constexpr (is_bf16<T>::value) {
             // the two top levels (Cin <= 128, >= 128^2 input pixels): one wave per strip, horizontal blur on the matrix cores,
             // no z tile (conv_upblur_rows.hpp).  Other bits than the tile kernels below, so the choice is by shape only.
             if (uprows_wanted<T>(a)) return launch_uprows<T>(a, stream);
@@ -2644,7 +2721,7 @@ int dispatch(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) 
             // The bits of the tile kernels below (same K order, same blur), so the choice may depend on the batch.
             if (upflat_wanted<T>(a)) return launch_upflat<T>(a, stream);
         }
-        if constexpr (sizeof(T) == 2) {
+        if constexpr (is_bf16<T>::value) {
             // single-chunk layers (the 1024^2 level) with >= 4 tiles per CU: persistent 8-wave workgroups on 16 x 16-quad tiles
             // -- the 36 KB of weights stay in LDS instead of being re-fetched by every tile (more than the tile's 28 KB
             // patch), the next patch flies during the blur, 8 waves keep the CU as busy as two 4-wave workgroups did.
@@ -2664,7 +2741,7 @@ int dispatch(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) 
             const char* te = getenv("VT_UPBLUR_TALL");
             const int64_t tall_min = te ? atoll(te) : 448;
             const int64_t wgs_tall = (int64_t)a.N * vt_cdiv(2 * a.H, 44) * vt_cdiv(2 * a.W, 28) * vt_cdiv(a.coutT, 32);
-            if constexpr (sizeof(T) == 2) {   // (the fp32 z tile of 47 x 31 pixels does not fit the LDS)
+            if constexpr (is_bf16<T>::value) {   // (the fp32 z tile of 47 x 31 pixels does not fit the LDS)
                 if (t.bn == 32 && !db && chunks >= (te ? 2 : 4) && tall_min > 0 && wgs_tall >= tall_min)
                     return launch_upblur<T, 32, 24, 0, 0, 0, 8>(a, stream);
             }
@@ -2688,7 +2765,7 @@ int dispatch(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) 
     if (t.kind == 6) return launch_thin<T>(a, stream);
     if (t.kind == 7) {
         GldsArgs gs;
-        if constexpr (sizeof(T) == 2) {
+        if constexpr (is_bf16<T>::value) {
             if (patchs2_eligible<T>(a, gs)) return t.bn == 32 ? launch_patchs2<T, 32>(a, gs, stream) : launch_patchs2<T, 64>(a, gs, stream);
         }
         vt_set_error("vt_conv2d: stride-2 patch kernel requested for an ineligible convolution");
@@ -2748,7 +2825,7 @@ int dispatch(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) 
             const bool pipe = !(e && e[0] == '0') && !a.x3;
             // one chunk of K, one channel tile, several tiles per CU: weights resident, persistent workgroups (VT_PATCH_PIPE=1:
             // the plain pipelined form, A/B)
-            if constexpr (sizeof(T) == 2) {
+            if constexpr (is_bf16<T>::value) {
                 // (lean epilogue: bf16 NHWC vector stores of all 64 channels, bias + (Leaky)ReLU * gain, optional fused ToRGB)
                 const bool lean = a.coutT == 64 && a.phases == 1 && a.out_layout == VT_OUT_NHWC && !a.out_f32 && a.vec_store &&
                                   a.ld_out % 8 == 0 && !a.resid && !a.slope_vec && !a.alpha_dev && !a.post_relu && !a.stats_part &&
@@ -2762,7 +2839,7 @@ int dispatch(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) 
             }
             // more tiles than CUs, whole K, lean epilogue: persistent workgroups, the pipeline runs across tile boundaries
             // (VT_PATCH_PIPE=1: one workgroup per tile, A/B).  VT_BATCH_EXACT or not: the same bits either way.
-            if constexpr (sizeof(T) == 2) {
+            if constexpr (is_bf16<T>::value) {
                 if (pipe && !(e && e[0] == '1') && a.dil == 1 && t.bm == 256 && (t.bn == 128 || t.bn == 64) && a.splitk <= 1 &&
                     conv_lean<T>(a) && vt_cdiv(a.coutT, t.bn) * t.bn * 8 <= PQ_TAB_BYTES &&   // (the tables of every channel tile, conv_patch_persist.hpp)
                     (int64_t)a.N * vt_cdiv(a.Ho, 16) * vt_cdiv(a.Wo, 16) * vt_cdiv(a.coutT, t.bn) > patchw_wgs()) {
@@ -2774,7 +2851,7 @@ int dispatch(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) 
             if (pipe && a.dil == 1 && t.bm == 256 && t.bn == 64) return launch_patchp<T, 16, 64, 4, 2, 4>(a, g, stream);
             // 32-channel tiles: all nine taps of a chunk resident, one barrier per chunk (conv_patch_chunk.hpp; VT_PATCH_PIPE=1:
             // the tap-granular pipeline, A/B -- same bits)
-            if constexpr (sizeof(T) == 2) {
+            if constexpr (is_bf16<T>::value) {
                 if (pipe && !(e && e[0] == '1') && a.dil == 1 && t.bm == 256 && t.bn == 32) return launch_patchc<T>(a, g, stream);
                 if (pipe && !(e && e[0] == '1') && a.dil == 2 && t.bm == 256 && t.bn == 32 && !a.stats_part)
                     return launch_patchc<T, 2>(a, g, stream);
@@ -2812,12 +2889,51 @@ int dispatch(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) 
     return VT_ERR_UNSUPPORTED;
 }
 
+// fp16 operands (the operator surface, vtoonify_amd/op): the generic 1-D tile kernels -- register-staged, or direct-to-LDS where
+// glds_eligible holds -- with split-K, fp16 NHWC or fp32 NCHW outputs.  No specialised family has an fp16 instance.
+template <typename T>
+int dispatch_generic(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) {
+    ConvArgs a = a0;
+    a.force_generic = hint >= 1000000000 || !axes_equal(a);
+    if (a.up_fir || a.rgb_w || a.rgb_only || a.in_absdiff || a.stats_part || a.tile_stats || a.in_tile_stats) {
+        vt_set_error("vt_conv2d: fp16 runs the generic tile kernels only (no up_fir, fused ToRGB, in_absdiff or statistics forms)");
+        return VT_ERR_UNSUPPORTED;
+    }
+    const TilePlan t = choose_plan<T>(a, hint % 1000000000, ws_floats);
+    if (t.kind != 0) {
+        vt_set_error("vt_conv2d: plan kind %d has no fp16 instance (fp16 runs the generic tile kernels only)", t.kind);
+        return VT_ERR_UNSUPPORTED;
+    }
+    a.splitk = t.splitk;
+    a.ldp = slab_ld(a.coutT);
+    const int bm = t.bm, bn = t.bn;
+#define VT_CFG(M_, N_, WM_, WN_) \
+    if (bm == M_ && bn == N_) return launch_cfg<T, M_, N_, WM_, WN_>(a, stream);
+    VT_CFG(128, 128, 2, 2)
+    VT_CFG(128, 64, 2, 2)
+    VT_CFG(128, 32, 4, 1)
+    VT_CFG(128, 16, 4, 1)
+    VT_CFG(64, 64, 2, 2)
+    VT_CFG(64, 128, 2, 2)
+#undef VT_CFG
+    vt_set_error("vt_conv2d: no compiled fp16 tile %dx%d", bm, bn);
+    return VT_ERR_UNSUPPORTED;
+}
+
+// the plan of a descriptor's compute dtype (vt_conv2d_tile / _splitk_mode / _ws_bytes)
+static TilePlan plan_of(const vt_conv_desc* d, const ConvArgs& a, int64_t ws_floats) {
+    const int hint = d->tile_hint % 1000000000;
+    if (d->dtype == VT_F16) return choose_plan<f16_t>(a, hint, ws_floats);
+    return d->dtype == VT_BF16 ? choose_plan<bf16_t>(a, hint, ws_floats) : choose_plan<float>(a, hint, ws_floats);
+}
+
 }  // namespace
 
 static int fill_args(const vt_conv_desc* d, ConvArgs& a) {
     VT_REQUIRE(d, "vt_conv2d: null descriptor");
     VT_REQUIRE(d->src0 && d->weight && d->out, "vt_conv2d: null tensor");
-    VT_REQUIRE(d->dtype == VT_F32 || d->dtype == VT_BF16 || d->dtype == VT_F32X3, "vt_conv2d: dtype must be fp32, bf16 or f32x3");
+    VT_REQUIRE(d->dtype == VT_F32 || d->dtype == VT_BF16 || d->dtype == VT_F16 || d->dtype == VT_F32X3,
+               "vt_conv2d: dtype must be fp32, bf16, fp16 or f32x3");
     const int cdt = d->dtype == VT_F32X3 ? VT_F32 : d->dtype;   // storage type of src*, weight
     VT_REQUIRE(d->c0 > 0 && d->c0 % 8 == 0 && d->c1 >= 0 && d->c1 % 8 == 0,
                "vt_conv2d: channel counts must be multiples of 8 (got %d,%d)", d->c0, d->c1);
@@ -2830,12 +2946,15 @@ static int fill_args(const vt_conv_desc* d, ConvArgs& a) {
     VT_REQUIRE(d->c1 == 0 || (((uintptr_t)d->src1 % 16 == 0) && ((int64_t)d->ld1 * esz % 16 == 0)),
                "vt_conv2d: src1 must be 16-byte aligned with 16-byte pixel stride");
     VT_REQUIRE(d->n > 0 && d->h > 0 && d->w > 0 && d->out_h > 0 && d->out_w > 0, "vt_conv2d: bad sizes");
-    VT_REQUIRE(d->kh > 0 && d->kw > 0 && d->stride > 0 && d->dil > 0 && d->cout > 0, "vt_conv2d: bad conv params");
+    VT_REQUIRE(d->kh > 0 && d->kw > 0 && (d->stride & 0xffff) > 0 && (d->dil & 0xffff) > 0 && d->stride > 0 && d->dil > 0 &&
+                   d->cout > 0, "vt_conv2d: bad conv params");
     VT_REQUIRE(d->phases == 1 || d->phases == 4, "vt_conv2d: phases must be 1 or 4");
     VT_REQUIRE(d->phases == 1 || (d->cout % 8 == 0 && d->out_layout == VT_OUT_NHWC && !d->transposed),
                "vt_conv2d: polyphase form needs cout %% 8 == 0 and NHWC output");
     VT_REQUIRE(d->out_layout == VT_OUT_NHWC || d->out_dtype == VT_F32, "vt_conv2d: NCHW output is fp32 only");
-    VT_REQUIRE(d->out_dtype == VT_F32 || d->out_dtype == VT_BF16, "vt_conv2d: bad out dtype");
+    VT_REQUIRE(d->dtype == VT_F16 ? (d->out_dtype == VT_F32 || d->out_dtype == VT_F16)
+                                  : (d->out_dtype == VT_F32 || d->out_dtype == VT_BF16),
+               "vt_conv2d: bad out dtype (VT_F32 or the 16-bit compute dtype)");
     VT_REQUIRE((int64_t)d->n * d->h * d->w < ((int64_t)1 << 31) &&
                    (int64_t)d->n * d->out_h * d->out_w * (d->phases == 4 ? 4 : 1) < ((int64_t)1 << 31),
                "vt_conv2d: tensor too large for 32-bit pixel indices");
@@ -2889,10 +3008,12 @@ static int fill_args(const vt_conv_desc* d, ConvArgs& a) {
     a.taps = d->kh * d->kw;
     a.kw = d->kw;
     a.K = a.taps * a.cin;
-    a.stride = d->stride;
+    a.stride = d->stride & 0xffff;   // low halves: vertical; high halves: horizontal, 0 = the same (ABI 5, per-axis geometry)
     a.pad = d->pad;
     a.pad_x = d->pad_w_p1 > 0 ? d->pad_w_p1 - 1 : d->pad;
-    a.dil = d->dil;
+    a.dil = d->dil & 0xffff;
+    a.stride_x = (d->stride >> 16) ? (d->stride >> 16) : a.stride;
+    a.dil_x = (d->dil >> 16) ? (d->dil >> 16) : a.dil;
     a.transposed = d->transposed;
     a.phases = d->phases;
     a.act = d->act;
@@ -2923,8 +3044,9 @@ extern "C" int vt_conv2d(const vt_conv_desc* d, vt_stream stream) {
     const int64_t wsf = (d->splitk_ws && d->splitk_ws_bytes > VT_TICKET_BYTES) ? (d->splitk_ws_bytes - VT_TICKET_BYTES) / 4 : 0;
     g_stats_emitted = false;
     a.x3 = d->dtype == VT_F32X3;
-    const int rcl = d->dtype == VT_BF16 ? dispatch<bf16_t>(a, d->tile_hint, wsf, stream)
-                                        : dispatch<float>(a, d->tile_hint, wsf, stream);
+    const int rcl = d->dtype == VT_F16    ? dispatch_generic<f16_t>(a, d->tile_hint, wsf, stream)
+                    : d->dtype == VT_BF16 ? dispatch<bf16_t>(a, d->tile_hint, wsf, stream)
+                                          : dispatch<float>(a, d->tile_hint, wsf, stream);
     if (rcl != VT_OK || !a.stats_part || g_stats_emitted || d->splitk_phase == 1) return rcl;
     // the plan had no reduce pass to carry the statistics: append the stand-alone launch
     return vt_internal_instnorm_partial(a.stats_part, d->out, d->ld_out, d->n, d->out_h * d->out_w, d->cout,
@@ -2934,14 +3056,15 @@ extern "C" int vt_conv2d(const vt_conv_desc* d, vt_stream stream) {
 extern "C" int vt_conv2d_tile(const vt_conv_desc* d) {
     ConvArgs a;
     if (fill_args(d, a) != VT_OK) return -1;
-    a.force_generic = d->tile_hint >= 1000000000 || a.pad_x != a.pad;
+    a.force_generic = d->tile_hint >= 1000000000 || !axes_equal(a);
     const int64_t wsf = (d->splitk_ws && d->splitk_ws_bytes > VT_TICKET_BYTES) ? (d->splitk_ws_bytes - VT_TICKET_BYTES) / 4 : 0;
-    const TilePlan t = d->dtype == VT_BF16 ? choose_plan<bf16_t>(a, d->tile_hint % 1000000000, wsf)
-                                           : choose_plan<float>(a, d->tile_hint % 1000000000, wsf);
+    const TilePlan t = plan_of(d, a, wsf);
     int kind = t.kind;
     if (kind == 0) {  // report which 1-D loader the launch will use: 2 = direct-to-LDS, 0 = register-staged
         GldsArgs g;
-        const bool glds = d->dtype == VT_BF16 ? glds_eligible<bf16_t>(a, g) : glds_eligible<float>(a, g);
+        const bool glds = d->dtype == VT_F16    ? glds_eligible<f16_t>(a, g)
+                          : d->dtype == VT_BF16 ? glds_eligible<bf16_t>(a, g)
+                                                : glds_eligible<float>(a, g);
         kind = glds ? 2 : 0;
     }
     int bm = t.bm, bn = t.bn;
@@ -2956,11 +3079,10 @@ extern "C" int vt_conv2d_tile(const vt_conv_desc* d) {
 extern "C" int vt_conv2d_splitk_mode(const vt_conv_desc* d) {
     ConvArgs a;
     if (fill_args(d, a) != VT_OK) return -1;
-    a.force_generic = d->tile_hint >= 1000000000 || a.pad_x != a.pad;
+    a.force_generic = d->tile_hint >= 1000000000 || !axes_equal(a);
     a.phase = d->splitk_phase;
     const int64_t wsf = (d->splitk_ws && d->splitk_ws_bytes > VT_TICKET_BYTES) ? (d->splitk_ws_bytes - VT_TICKET_BYTES) / 4 : 0;
-    const TilePlan t = d->dtype == VT_BF16 ? choose_plan<bf16_t>(a, d->tile_hint % 1000000000, wsf)
-                                           : choose_plan<float>(a, d->tile_hint % 1000000000, wsf);
+    const TilePlan t = plan_of(d, a, wsf);
     if (t.splitk <= 1) return 0;
     // the tile grid of the launch (launch_cfg / launch_patch): 1-D tiles of bm pixels, or bm/16 x 16-pixel tiles
     const int64_t tiles_m = t.kind == 1 ? (int64_t)a.N * vt_cdiv(a.Ho, t.bm / 16) * vt_cdiv(a.Wo, 16) : vt_cdiv(a.M, t.bm);
@@ -2970,12 +3092,11 @@ extern "C" int vt_conv2d_splitk_mode(const vt_conv_desc* d) {
 extern "C" int64_t vt_conv2d_ws_bytes(const vt_conv_desc* d) {
     ConvArgs a;
     if (fill_args(d, a) != VT_OK) return -1;
-    a.force_generic = d->tile_hint >= 1000000000 || a.pad_x != a.pad;
+    a.force_generic = d->tile_hint >= 1000000000 || !axes_equal(a);
     float dummy;
     a.partial = &dummy;  // "a workspace of any size exists": report what the heuristic would use
     const int64_t big = (int64_t)1 << 40;
-    const TilePlan t = d->dtype == VT_BF16 ? choose_plan<bf16_t>(a, d->tile_hint % 1000000000, big)
-                                           : choose_plan<float>(a, d->tile_hint % 1000000000, big);
+    const TilePlan t = plan_of(d, a, big);
     if (t.splitk <= 1) return 0;
     return VT_TICKET_BYTES + (int64_t)t.splitk * a.M * slab_ld(a.coutT) * 4;
 }
@@ -3034,6 +3155,9 @@ extern "C" int vt_mfma_selftest(float* c, const void* a, const void* b, int dtyp
     if (dtype == VT_BF16) {
         auto k = mfma_selftest_kernel<bf16_t>;
         VT_LAUNCH(k, dim3(1), dim3(64), stream, c, (const bf16_t*)a, (const bf16_t*)b);
+    } else if (dtype == VT_F16) {
+        auto k = mfma_selftest_kernel<f16_t>;
+        VT_LAUNCH(k, dim3(1), dim3(64), stream, c, (const f16_t*)a, (const f16_t*)b);
     } else if (dtype == VT_F32) {
         auto k = mfma_selftest_kernel<float>;
         VT_LAUNCH(k, dim3(1), dim3(64), stream, c, (const float*)a, (const float*)b);

@@ -187,7 +187,7 @@ template <typename T>
 static bool patchs2_eligible(const ConvArgs& a, GldsArgs& g) {
     constexpr int ESZ = (int)sizeof(T);
     constexpr int BK = 8 * (16 / ESZ);
-    if (a.force_generic || a.transposed || a.in_scale || a.src1 || a.c1 != 0 || a.x3) return false;
+    if (a.force_generic || !axes_equal(a) || a.transposed || a.in_scale || a.src1 || a.c1 != 0 || a.x3) return false;
     if (a.stride != 2 || a.taps != 9 || a.kw != 3 || a.pad != 1 || a.pad_x != 1 || a.dil != 1 || a.phases != 1) return false;
     if (a.H % 2 || a.W % 2 || a.Ho != a.H / 2 || a.Wo != a.W / 2) return false;
     if (a.c0 % BK != 0 || a.cin != a.c0 || a.coutT % 8 != 0) return false;

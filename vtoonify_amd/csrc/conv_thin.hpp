@@ -27,7 +27,7 @@ constexpr int TH_PADC = 4;          // floats of padding per d row (LDS banks)
 template <typename T>
 static bool thin_eligible(const ConvArgs& a) {
     constexpr int KSTEP = 4 * (16 / (int)sizeof(T));
-    if (a.force_generic || a.transposed || a.rgb_w || a.stats_part || a.tile_stats || a.in_tile_stats || a.up_fir || a.slope_vec)
+    if (a.force_generic || !axes_equal(a) || a.transposed || a.rgb_w || a.stats_part || a.tile_stats || a.in_tile_stats || a.up_fir || a.slope_vec)
         return false;
     if (a.in_scale && !a.in_shift) return false;
     if ((a.in_scale || a.in_absdiff) && !(a.taps == 9 && a.taps * a.coutT <= 16)) return false;   // the compiled prologue form

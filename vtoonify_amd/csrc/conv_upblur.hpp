@@ -422,7 +422,7 @@ template <typename T>
 static bool upblur_eligible(const ConvArgs& a, UpblurArgs& g, int ty, int tx) {
     constexpr int ESZ = (int)sizeof(T);
     constexpr int BK = 8 * (16 / ESZ);
-    if (!a.up_fir || a.transposed || a.in_scale || a.rgb_w || a.resid || a.c1 != 0 || a.post_relu) return false;
+    if (!a.up_fir || !axes_equal(a) || a.transposed || a.in_scale || a.rgb_w || a.resid || a.c1 != 0 || a.post_relu) return false;
     if (a.taps != 9 || a.kw != 3 || a.phases != 1 || a.Ho != 2 * a.H || a.Wo != 2 * a.W) return false;
     if (a.cin % BK != 0 || a.coutT % 8 != 0) return false;
     if (a.act != VT_ACT_NONE && a.act != VT_ACT_LRELU) return false;

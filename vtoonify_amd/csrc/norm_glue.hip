@@ -824,12 +824,15 @@ static int nchw_to_nhwc_out(void* out, int ld_out, const TI* in, int n, int c, i
 #undef VT_PIX
         return vt_check_launch("vt_nchw_to_nhwc");
     }
-    if (cpad > 32 && (out_dtype == VT_F32 || out_dtype == VT_BF16) && ((int64_t)ld_out * osz) % 16 == 0 &&
+    if (cpad > 32 && (out_dtype == VT_F32 || out_dtype == VT_BF16 || out_dtype == VT_F16) && ((int64_t)ld_out * osz) % 16 == 0 &&
         (uintptr_t)out % 16 == 0) {   // wide tensors: tiles through LDS
         const unsigned grid = tile_grid(n, hw, cpad);
         if (out_dtype == VT_F32) {
             auto k = nchw_to_nhwc_tile_kernel<TI, float>;
             VT_LAUNCH(k, dim3(grid), dim3(256), stream, (float*)out, ld_out, in, n, c, hw, cpad);
+        } else if (out_dtype == VT_F16) {
+            auto k = nchw_to_nhwc_tile_kernel<TI, f16_t>;
+            VT_LAUNCH(k, dim3(grid), dim3(256), stream, (f16_t*)out, ld_out, in, n, c, hw, cpad);
         } else {
             auto k = nchw_to_nhwc_tile_kernel<TI, bf16_t>;
             VT_LAUNCH(k, dim3(grid), dim3(256), stream, (bf16_t*)out, ld_out, in, n, c, hw, cpad);
@@ -842,6 +845,9 @@ static int nchw_to_nhwc_out(void* out, int ld_out, const TI* in, int n, int c, i
     } else if (out_dtype == VT_BF16) {
         auto k = nchw_to_nhwc_kernel<TI, bf16_t>;
         VT_LAUNCH(k, dim3(grid_for(total)), dim3(256), stream, (bf16_t*)out, ld_out, in, n, c, hw, cpad);
+    } else if (out_dtype == VT_F16) {
+        auto k = nchw_to_nhwc_kernel<TI, f16_t>;
+        VT_LAUNCH(k, dim3(grid_for(total)), dim3(256), stream, (f16_t*)out, ld_out, in, n, c, hw, cpad);
     } else {
         vt_set_error("vt_nchw_to_nhwc: out dtype");
         return VT_ERR_UNSUPPORTED;
@@ -864,12 +870,15 @@ template <typename TI>
 static int nhwc_to_nchw_out(void* out, const TI* in, int ld_in, int n, int c, int hw, int out_dtype,
                             vt_stream stream) {
     const int64_t total = (int64_t)n * c * hw;
-    if (c >= 32 && c % 8 == 0 && (out_dtype == VT_F32 || out_dtype == VT_BF16) &&
+    if (c >= 32 && c % 8 == 0 && (out_dtype == VT_F32 || out_dtype == VT_BF16 || out_dtype == VT_F16) &&
         ((int64_t)ld_in * (int64_t)sizeof(TI)) % 16 == 0 && (uintptr_t)in % 16 == 0) {   // wide tensors: tiles through LDS
         const unsigned grid = tile_grid(n, hw, c);
         if (out_dtype == VT_F32) {
             auto k = nhwc_to_nchw_tile_kernel<TI, float>;
             VT_LAUNCH(k, dim3(grid), dim3(256), stream, (float*)out, in, ld_in, n, c, hw);
+        } else if (out_dtype == VT_F16) {
+            auto k = nhwc_to_nchw_tile_kernel<TI, f16_t>;
+            VT_LAUNCH(k, dim3(grid), dim3(256), stream, (f16_t*)out, in, ld_in, n, c, hw);
         } else {
             auto k = nhwc_to_nchw_tile_kernel<TI, bf16_t>;
             VT_LAUNCH(k, dim3(grid), dim3(256), stream, (bf16_t*)out, in, ld_in, n, c, hw);
@@ -897,6 +906,7 @@ extern "C" int vt_nhwc_to_nchw(void* out, const void* in, int ld_in, int n, int 
     VT_REQUIRE(out && in && n > 0 && c > 0 && hw > 0 && ld_in >= c, "vt_nhwc_to_nchw: bad arguments");
     if (in_dtype == VT_F32) return nhwc_to_nchw_out<float>(out, (const float*)in, ld_in, n, c, hw, out_dtype, stream);
     if (in_dtype == VT_BF16) return nhwc_to_nchw_out<bf16_t>(out, (const bf16_t*)in, ld_in, n, c, hw, out_dtype, stream);
+    if (in_dtype == VT_F16) return nhwc_to_nchw_out<f16_t>(out, (const f16_t*)in, ld_in, n, c, hw, out_dtype, stream);
     vt_set_error("vt_nhwc_to_nchw: in dtype");
     return VT_ERR_UNSUPPORTED;
 }

@@ -399,6 +399,9 @@ extern "C" int vt_pack_conv_weight(void* out, const float* w, int cout, int cin_
     } else if (out_dtype == VT_BF16) {
         auto kf = pack_weight_kernel<bf16_t>;
         VT_LAUNCH(kf, grid, block, stream, (bf16_t*)out, w, cout, cin_src, kh, kw, cin_dst, chan_map, scale, src_transposed);
+    } else if (out_dtype == VT_F16) {
+        auto kf = pack_weight_kernel<f16_t>;
+        VT_LAUNCH(kf, grid, block, stream, (f16_t*)out, w, cout, cin_src, kh, kw, cin_dst, chan_map, scale, src_transposed);
     } else {
         vt_set_error("vt_pack_conv_weight: unsupported dtype %d", out_dtype);
         return VT_ERR_UNSUPPORTED;

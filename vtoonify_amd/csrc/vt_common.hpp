@@ -219,6 +219,15 @@ __device__ __forceinline__ u128 pack16<bf16_t>(const float* f) {
     v.w = pack_bf16x2(f[6], f[7]);
     return v;
 }
+template <>
+__device__ __forceinline__ u128 pack16<f16_t>(const float* f) {   // round-to-nearest-even per element
+    f16_t h[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) h[i] = from_f32<f16_t>(f[i]);
+    u128 v;
+    memcpy(&v, h, 16);
+    return v;
+}
 
 // ---------------------------------------------------------------------------------
 // buffer descriptor + direct-to-LDS 16-byte load (buffer_load_dwordx4 ... offen lds)

@@ -97,6 +97,13 @@ def _ptr(v):
     return int(v)
 
 
+def _axes(v):
+    """An int or an (h, w) pair -> (h, w)."""
+    if isinstance(v, (tuple, list)):
+        return int(v[0]), int(v[1])
+    return int(v), int(v)
+
+
 def make_conv_desc(*, src0, c0, ld0, n, h, w, out_h, out_w, weight, cout, kh, kw, out, ld_out, dtype,
                    src1=None, c1=0, ld1=0, stride=1, pad=0, dil=1, phases=1, transposed=0, in_scale=None,
                    in_shift=None, bias=None, act=ACT_NONE, slope=0.2, gain=1.0, alpha=1.0, beta=0.0,
@@ -104,7 +111,15 @@ def make_conv_desc(*, src0, c0, ld0, n, h, w, out_h, out_w, weight, cout, kh, kw
                    tile_hint=0, splitk_ws=None, slope_vec=None, rgb_weight=None, rgb_bias=None, rgb_resid=None,
                    rgb_out=None, stats_part=None, post_relu=0, weight_stream=None, tile_stats=None,
                    in_tile_stats=None, in_stats_dil=1, in_gb=None, in_ld_gb=0, up_fir=None, pad_w=None, rgb_only=0, in_absdiff=0) -> ConvDesc:
-    """Fill a vt_conv_desc.  Pointers may be tensors or raw ints (sub-views: data_ptr()+offset)."""
+    """Fill a vt_conv_desc.  Pointers may be tensors or raw ints (sub-views: data_ptr()+offset).
+    stride / pad / dil may be (h, w) pairs: a horizontal stride / dilation that differs goes to the high half of the field,
+    a horizontal pad that differs to pad_w (an explicit pad_w wins).  Equal pairs give the descriptor of the int form."""
+    (sh, sw), (dh, dw) = _axes(stride), _axes(dil)
+    stride = sh if sw == sh else sh | (sw << 16)
+    dil = dh if dw == dh else dh | (dw << 16)
+    pad, pad_wx = _axes(pad)
+    if pad_w is None and pad_wx != pad:
+        pad_w = pad_wx
     d = ConvDesc()
     d.src0, d.src1 = _ptr(src0), _ptr(src1)
     d.c0, d.c1, d.ld0, d.ld1 = c0, c1, ld0, ld1
@@ -140,6 +155,7 @@ def make_conv_desc(*, src0, c0, ld0, n, h, w, out_h, out_w, weight, cout, kh, kw
 
 
 def conv2d(*, stream_of=None, **kw):
+    """vt_conv2d; stride / pad / dil may be (h, w) pairs (make_conv_desc)."""
     d = make_conv_desc(**kw)
     t = stream_of
     if t is None:

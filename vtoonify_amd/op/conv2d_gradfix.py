@@ -4,9 +4,11 @@ module globals `enabled` / `weight_gradients_disabled`, `no_weight_gradients()`,
 
 On the reference every call ends in cuDNN via F.conv2d / F.conv_transpose2d; here GPU
 tensors run the MFMA implicit-GEMM kernel of libvtoonify_amd.so (fp32 inputs use the exact
-fp32 MFMA, bf16 inputs the bf16 MFMA); CPU tensors end in F.conv2d / F.conv_transpose2d like the
+fp32 MFMA, bf16 inputs the bf16 MFMA, fp16 inputs the fp16 MFMA); CPU tensors end in F.conv2d / F.conv_transpose2d like the
 reference's (its could_use_op() is False off the GPU, op/conv2d_gradfix.py:78-92).  `groups` (the per-sample trick of ModulatedConv2d,
-model.py:273-304) is a loop of launches.
+model.py:273-304) is a loop of launches.  stride / padding / dilation / output_padding are an int or an (h, w) pair, as the
+reference's ensure_tuple (op/conv2d_gradfix.py:95-98) takes them; a pair whose axes differ runs on the generic tile kernel
+(the high halves of vt_conv_desc.stride / dil).  fp64 is not supported on the GPU.
 
 Autograd follows the reference's structure (op/conv2d_gradfix.py:134-223), every contraction on the
 same HIP kernel family:
@@ -21,6 +23,7 @@ same HIP kernel family:
 """
 import contextlib
 import ctypes as C
+import operator
 
 import torch
 
@@ -41,34 +44,38 @@ def no_weight_gradients():
     weight_gradients_disabled = old
 
 
-def _one(v, what):
-    if isinstance(v, (tuple, list)):
-        if len(set(int(i) for i in v)) != 1:
-            raise NotImplementedError(f"{what} must be the same on both axes")
-        return int(v[0])
-    return int(v)
-
-
 def _pair(v, what):
+    """An int or a 2-sequence -> (h, w) (the reference's ensure_tuple); anything else is a ValueError."""
     if isinstance(v, (tuple, list)):
         if len(v) != 2:
-            raise ValueError(f"{what} must be an int or a pair")
+            raise ValueError(f"{what} must be an int or a pair, got {v!r}")
         return int(v[0]), int(v[1])
-    return int(v), int(v)
+    try:
+        v = operator.index(v)
+    except TypeError:
+        raise ValueError(f"{what} must be an int or a pair, got {v!r}") from None
+    return v, v
+
+
+def _k(v):
+    """A pair as the kernel descriptor takes it: the int when both axes agree (the descriptor of the int form)."""
+    return v[0] if v[0] == v[1] else v
 
 
 def _check(input, weight):
     if input.ndim != 4 or weight.ndim != 4:
         raise ValueError("expected 4-D input and weight")
-    if input.dtype not in (torch.float32, torch.bfloat16):
-        raise NotImplementedError("conv2d_gradfix supports fp32 and bf16 inputs")
+    if input.dtype == torch.float64:
+        raise NotImplementedError("conv2d_gradfix runs fp32, bf16 and fp16 tensors on the GPU; fp64 is not supported there "
+                                  "(CPU tensors take F.conv2d / F.conv_transpose2d)")
+    if input.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise NotImplementedError(f"conv2d_gradfix supports fp32, bf16 and fp16 inputs, got {input.dtype}")
 
 
 def _launch(input, weight, bias, stride, padding, dilation, groups, transposed, output_padding):
-    """One forward contraction (no autograd): F.conv2d / F.conv_transpose2d semantics."""
+    """One forward contraction (no autograd): F.conv2d / F.conv_transpose2d semantics.  Geometry: (h, w) pairs."""
     _check(input, weight)
-    stride, padding, dilation = _one(stride, "stride"), _one(padding, "padding"), _one(dilation, "dilation")
-    oph, opw = _pair(output_padding, "output_padding")
+    (sh, sw), (ph, pw), (dh, dw), (oph, opw) = stride, padding, dilation, output_padding
     dtype = input.dtype
     n, cin, h, w = input.shape
     if transposed:
@@ -76,15 +83,15 @@ def _launch(input, weight, bias, stride, padding, dilation, groups, transposed, 
         if cin_w != cin:
             raise ValueError("conv_transpose2d: weight.shape[0] must equal input channels")
         cout = cout_g * groups
-        out_h = (h - 1) * stride - 2 * padding + dilation * (kh - 1) + oph + 1
-        out_w = (w - 1) * stride - 2 * padding + dilation * (kw - 1) + opw + 1
+        out_h = (h - 1) * sh - 2 * ph + dh * (kh - 1) + oph + 1
+        out_w = (w - 1) * sw - 2 * pw + dw * (kw - 1) + opw + 1
     else:
         cout, cin_g, kh, kw = weight.shape
         if cin_g * groups != cin:
             raise ValueError("conv2d: weight.shape[1] * groups must equal input channels")
         cout_g = cout // groups
-        out_h = (h + 2 * padding - dilation * (kh - 1) - 1) // stride + 1
-        out_w = (w + 2 * padding - dilation * (kw - 1) - 1) // stride + 1
+        out_h = (h + 2 * ph - dh * (kh - 1) - 1) // sh + 1
+        out_w = (w + 2 * pw - dw * (kw - 1) - 1) // sw + 1
     if out_h <= 0 or out_w <= 0:
         raise ValueError("convolution output would be empty")
     cin_g = cin // groups
@@ -95,8 +102,10 @@ def _launch(input, weight, bias, stride, padding, dilation, groups, transposed, 
     # conv_transpose2d with stride 1 IS a convolution with the kernel turned by 180 degrees and the channel axes swapped
     # (padding d*(k-1) - p): it takes the patch kernels of the forward pass instead of the gather form -- this is the
     # grad_input of every stride-1 convolution (op/conv2d_gradfix.py:147-160 in the reference).  Data movement on the weight only.
-    as_conv = transposed and stride == 1 and oph == 0 and opw == 0 and dilation * (kh - 1) - padding >= 0 and kh == kw
-    conv_pad = dilation * (kh - 1) - padding if as_conv else padding
+    # Per axis: padding d*(k-1) - p must be >= 0 on both axes, otherwise the gather form.
+    as_conv = (transposed and sh == 1 and sw == 1 and oph == 0 and opw == 0 and dh * (kh - 1) - ph >= 0 and
+               dw * (kw - 1) - pw >= 0)
+    conv_pad = (dh * (kh - 1) - ph, dw * (kw - 1) - pw) if as_conv else (ph, pw)
     # wide outputs: NHWC out of the fast epilogues + one tiled layout change (vt_nhwc_to_nchw); narrow ones (ToRGB, masks)
     # keep the planar output of the thin kernels
     via_nhwc = cout_g >= 32 and cout_g % 8 == 0
@@ -117,7 +126,7 @@ def _launch(input, weight, bias, stride, padding, dilation, groups, transposed, 
             wp = K.pack_conv_weight(wg, cin_dst=cpad, out_dtype=dtype)
         bg = b32[g * cout_g:(g + 1) * cout_g].contiguous() if b32 is not None else None
         common = dict(src0=x_nhwc, c0=cpad, ld0=cpad, n=n, h=h, w=w, out_h=out_h, out_w=out_w, weight=wp, cout=cout_g, kh=kh,
-                      kw=kw, stride=stride, pad=conv_pad, dil=dilation, transposed=int(transposed and not as_conv), bias=bg,
+                      kw=kw, stride=_k(stride), pad=_k(conv_pad), dil=_k(dilation), transposed=int(transposed and not as_conv), bias=bg,
                       dtype=K.dt_code(dtype))
         if via_nhwc:
             o_nhwc = torch.empty((n, out_h, out_w, cout_g), dtype=dtype, device=input.device)
@@ -139,8 +148,8 @@ def _output_padding(cfg, input_shape, output_shape, weight_shape):
     transposed, stride, padding, _, dilation = cfg
     if transposed:
         return (0, 0)
-    return tuple(input_shape[i + 2] - (output_shape[i + 2] - 1) * stride - (1 - 2 * padding)
-                 - dilation * (weight_shape[i + 2] - 1) for i in range(2))
+    return tuple(input_shape[i + 2] - (output_shape[i + 2] - 1) * stride[i] - (1 - 2 * padding[i])
+                 - dilation[i] * (weight_shape[i + 2] - 1) for i in range(2))
 
 
 _GW_CHUNK_BYTES = 1 << 28   # one im2col operand per GEMM launch stays below this (transient memory of a backward conv: the A
@@ -150,7 +159,7 @@ _GW_CHUNK_BYTES = 1 << 28   # one im2col operand per GEMM launch stays below thi
 
 
 def _grad_weight_kernel(inp, grad, kh, kw, stride, padding, dilation):
-    """dW[c_grad, c_inp, ky, kx] = sum_{n,oy,ox} grad[n,c_grad,oy,ox] * inp[n,c_inp,oy*s+ky*d-p,ox*s+kx*d-p]
+    """dW[c_grad, c_inp, ky, kx] = sum_{n,oy,ox} grad[n,c_grad,oy,ox] * inp[n,c_inp,oy*sh+ky*dh-ph,ox*sw+kx*dw-pw]
     (what the reference gets from cudnn_convolution_backward_weight, op/conv2d_gradfix.py:188-223).
 
     The PIXELS are the contraction axis: with A[(tap, c_inp)][(n,oy,ox)] = the tap's shifted, strided view of the
@@ -162,14 +171,14 @@ def _grad_weight_kernel(inp, grad, kh, kw, stride, padding, dilation):
     Batches too large for one operand are cut into groups of images / rows; their fp32 partial results are added."""
     n, ca, h, w = inp.shape
     n2, cb, ho, wo = grad.shape
-    s, p, d = stride, padding, dilation
-    if n2 != n or (ho - 1) * s + (kh - 1) * d + 1 > h + 2 * p or (wo - 1) * s + (kw - 1) * d + 1 > w + 2 * p:
+    (sh, sw), (ph, pw), (dh, dw) = stride, padding, dilation
+    if n2 != n or (ho - 1) * sh + (kh - 1) * dh + 1 > h + 2 * ph or (wo - 1) * sw + (kw - 1) * dw + 1 > w + 2 * pw:
         raise ValueError("conv2d_gradfix: inconsistent shapes in the weight gradient")
     dtype, dev = inp.dtype, inp.device
-    esz = 4 if dtype == torch.float32 else 2
+    esz = 4 if dtype == torch.float32 else 2          # (bf16 / fp16: the A operand in the compute dtype)
     taps = kh * kw
     m = taps * ca
-    xp = torch.nn.functional.pad(inp.detach(), (p, p, p, p)).transpose(0, 1)     # (Ca, N, Hp, Wp) view
+    xp = torch.nn.functional.pad(inp.detach(), (pw, pw, ph, ph)).transpose(0, 1)   # (Ca, N, Hp, Wp) view
     gt = grad.detach().transpose(0, 1)                                            # (Cb, N, Ho, Wo) view
     # groups of (images, output rows) whose operands fit the chunk size
     per_row = max(m * esz, cb * (4 + esz)) * wo          # A rows, or grad_output's fp32 copy + its packed form
@@ -190,9 +199,9 @@ def _grad_weight_kernel(inp, grad, kh, kw, stride, padding, dilation):
             a[:, :, k:].zero_()
         for ky in range(kh):
             for kx in range(kw):
-                r0, c0 = ky * d + y0 * s, kx * d
+                r0, c0 = ky * dh + y0 * sh, kx * dw
                 a[ky * kw + kx, :, :k].unflatten(1, (ni, rows, wo)).copy_(
-                    xp[:, n0:n1, r0:r0 + s * (rows - 1) + 1:s, c0:c0 + s * (wo - 1) + 1:s])
+                    xp[:, n0:n1, r0:r0 + sh * (rows - 1) + 1:sh, c0:c0 + sw * (wo - 1) + 1:sw])
         b = gt[:, n0:n1, y0:y1].reshape(cb, k, 1, 1).to(torch.float32).contiguous()
         wp = K.pack_conv_weight(b, cin_dst=kp, out_dtype=dtype)
         out = torch.empty((1, cb, 1, m), dtype=torch.float32, device=dev)
@@ -209,7 +218,7 @@ def _grad_weight_kernel(inp, grad, kh, kw, stride, padding, dilation):
 
 
 class _Conv(torch.autograd.Function):
-    """groups == 1.  cfg = (transposed, stride, padding, output_padding, dilation)."""
+    """groups == 1.  cfg = (transposed, stride, padding, output_padding, dilation), geometry as (h, w) pairs."""
 
     @staticmethod
     def forward(ctx, input, weight, bias, cfg):
@@ -265,12 +274,13 @@ def _run(input, weight, bias, stride, padding, dilation, groups, transposed, out
             return native.conv_transpose2d(input, weight, bias, stride, padding, output_padding, groups, dilation)
         return native.conv2d(input, weight, bias, stride, padding, dilation, groups)
     _check(input, weight)
+    stride, padding, dilation = _pair(stride, "stride"), _pair(padding, "padding"), _pair(dilation, "dilation")
+    output_padding = _pair(output_padding, "output_padding")
     needs_grad = torch.is_grad_enabled() and (input.requires_grad or weight.requires_grad or
                                               (bias is not None and bias.requires_grad))
     if not needs_grad:
         return _launch(input, weight, bias, stride, padding, dilation, groups, transposed, output_padding)
-    stride, padding, dilation = _one(stride, "stride"), _one(padding, "padding"), _one(dilation, "dilation")
-    cfg = (bool(transposed), stride, padding, _pair(output_padding, "output_padding"), dilation)
+    cfg = (bool(transposed), stride, padding, output_padding, dilation)
     if groups == 1:
         return _Conv.apply(input, weight, bias, cfg)
     # grouped convolution (ModulatedConv2d folds the batch into groups, model.py:273-304): one
