@@ -3,6 +3,7 @@
 alternating the arms REPS times on one box:
 
     python tools/ab_engine.py "fuse_rgb128=True" "fuse_rgb128=False" [--reps 3] [--steps 60] [--batch 4] [--size 256]
+    python tools/ab_engine.py "dtype=float16" "dtype=bfloat16"      # the compute precision as an arm (default bfloat16)
 
 Prints frames/s per arm and repetition, and the per-launch times (HIP events, engine.time_ops) of the same-resolution
 StyledConv / ToRGB launches of each arm."""
@@ -56,6 +57,7 @@ class arm_env:   # the arm's environment switches, for the duration of a with-bl
 
 for a in args:
     kw = {}
+    dtype = torch.bfloat16
     for kv in a.split(","):
         k, v = kv.split("=")
         if k == "hints":   # hints=FILE.json: a tile-hint table {conv signature: tile_hint} (engine.conv_signature)
@@ -63,13 +65,15 @@ for a in args:
             kw["tile_hints"] = {kk: int(vv) for kk, vv in json.load(open(v)).items()}
         elif k == "env":   # env=NAME:VALUE: an environment switch of the library, set while this arm builds plans, captures and runs
             envs.setdefault(a, {})[v.split(":")[0]] = v.split(":")[1]
+        elif k == "dtype":   # dtype=float16 / bfloat16 / float32: the engine's compute precision
+            dtype = getattr(torch, v)
         elif k == "lib":   # lib=PATH: an experiment build of the library (vtoonify_amd.build --variant); an engine keeps the
             libpath = v    # handle it was constructed with, so arms with different libraries coexist in one process
         else:
             kw[k] = ast.literal_eval(v)
     from vtoonify_amd import _lib
     _lib.use_library(locals().pop("libpath", None) or _lib.DEFAULT_LIB)
-    arms.append((a, VToonifyEngine(sd, "dualstylegan", 256, torch.bfloat16, dev, **kw)))
+    arms.append((a, VToonifyEngine(sd, "dualstylegan", 256, dtype, dev, **kw)))
     _lib.use_library(_lib.DEFAULT_LIB)
 
 

@@ -68,7 +68,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--batch_size", type=int, default=4, help="batch size of frames when processing video")
     p.add_argument("--parsing_map_path", type=str, default=None, help="path of the refined parsing map of the target video")
     # ---- additions of this driver ----
-    p.add_argument("--precision", choices=["fp32", "fp32_exact", "bf16"], default=None,
+    p.add_argument("--precision", choices=["fp32", "fp32_exact", "bf16", "fp16"], default=None,
                    help="arithmetic of the frame (default: VTOONIFY_AMD_DTYPE or fp32 = the reference's precision)")
     p.add_argument("--depth", type=int, default=3, help="batches in flight per GPU (each on its own stream and plan)")
     p.add_argument("--frame_order", choices=["bgr", "rgb"], default="bgr", help="channel order of .npy frames (cv2 files are BGR)")
@@ -351,7 +351,7 @@ def main(argv=None, device=None, backend=None) -> dict:
         torch.cuda.set_device(device)
     on_engine = device.type == "cuda" or _lib.emulation_injected()
     prec = opt.precision or os.environ.get("VTOONIFY_AMD_DTYPE", "fp32")
-    cdt = torch.bfloat16 if prec == "bf16" else torch.float32
+    cdt = torch.bfloat16 if prec == "bf16" else torch.float16 if prec in ("fp16", "float16") else torch.float32
 
     src = open_source(opt.content, opt.video, opt.frame_order)
     n = len(src) if opt.max_frames is None else min(len(src), opt.max_frames)
@@ -382,7 +382,8 @@ def main(argv=None, device=None, backend=None) -> dict:
 
     # ---- parsing maps: given (--parsing_map_path, style_transfer.py:168-169) or computed on the GPU (:170-172) ----
     maps = np.load(opt.parsing_map_path, mmap_mode="r") if (opt.video and opt.parsing_map_path) else None
-    par = None if maps is not None else parsing_engine(opt, device, cdt)
+    # (the parsing network has no fp16 form: it runs in bf16 beside an fp16 frame)
+    par = None if maps is not None else parsing_engine(opt, device, torch.bfloat16 if cdt == torch.float16 else cdt)
 
     base = os.path.basename(opt.content.rstrip("/")).split(".")[0]
     stem = os.path.join(opt.output_path, f"{base}_vtoonify_{opt.backbone[0]}")

@@ -337,7 +337,7 @@ conv_fullk_kernel(const ConvArgs p, const FullkArgs g) {
     for (int i = 0; i < 4; ++i) f[i] = conv_finish(p, f[i], ep_bias[i], ga, ep_slope[i]);
     const int m = (img * p.H + oy) * p.W + ox;
     if (!p.tile_stats) {
-        if (live) store_out4(p, m, n, f);
+        if (live) store_out4<typename Out16<T>::type>(p, m, n, f);
         return;
     }
     // ---- output + its InstanceNorm tile record (host guarantees NHWC, T-typed, 8-byte aligned vector stores) ----
@@ -345,10 +345,10 @@ conv_fullk_kernel(const ConvArgs p, const FullkArgs g) {
     if (live) {
         if (p.resid) {
             float g4[4];
-            if (sizeof(T) == 2) {
-                const u64v rv = *reinterpret_cast<const u64v*>((const bf16_t*)p.resid + (int64_t)m * p.ld_res + n);
-                g4[0] = vt_u2f(rv.x << 16); g4[1] = vt_u2f(rv.x & 0xffff0000u);
-                g4[2] = vt_u2f(rv.y << 16); g4[3] = vt_u2f(rv.y & 0xffff0000u);
+            if constexpr (sizeof(T) == 2) {
+                const u64v rv = *reinterpret_cast<const u64v*>((const T*)p.resid + (int64_t)m * p.ld_res + n);
+                unpack2<T>(rv.x, g4[0], g4[1]);
+                unpack2<T>(rv.y, g4[2], g4[3]);
             } else {
                 unpack16<float>(ld128((const float*)p.resid + (int64_t)m * p.ld_res + n), g4);
             }
@@ -356,13 +356,13 @@ conv_fullk_kernel(const ConvArgs p, const FullkArgs g) {
             for (int i = 0; i < 4; ++i) f[i] += p.beta * g4[i];
         }
         post_act_n<4>(p, f);
-        if (sizeof(T) == 2) {
+        if constexpr (sizeof(T) == 2) {
             u64v v;
-            v.x = pack_bf16x2(f[0], f[1]);
-            v.y = pack_bf16x2(f[2], f[3]);
-            *reinterpret_cast<u64v*>((bf16_t*)p.out + (int64_t)m * p.ld_out + n) = v;
-            f[0] = vt_u2f(v.x << 16); f[1] = vt_u2f(v.x & 0xffff0000u);
-            f[2] = vt_u2f(v.y << 16); f[3] = vt_u2f(v.y & 0xffff0000u);
+            v.x = pack2<T>(f[0], f[1]);
+            v.y = pack2<T>(f[2], f[3]);
+            *reinterpret_cast<u64v*>((T*)p.out + (int64_t)m * p.ld_out + n) = v;
+            unpack2<T>(v.x, f[0], f[1]);
+            unpack2<T>(v.y, f[2], f[3]);
         } else {
             st128((float*)p.out + (int64_t)m * p.ld_out + n, pack16<float>(f));
         }

@@ -393,9 +393,9 @@ conv_fullkw_kernel(const ConvArgs p, const FullkwArgs g) {
                 if (live) {
                     if (p.resid) {
                         float g4[4];
-                        if (sizeof(T) == 2) {
-                            g4[0] = vt_u2f(rv.x << 16); g4[1] = vt_u2f(rv.x & 0xffff0000u);
-                            g4[2] = vt_u2f(rv.y << 16); g4[3] = vt_u2f(rv.y & 0xffff0000u);
+                        if constexpr (sizeof(T) == 2) {
+                            unpack2<T>(rv.x, g4[0], g4[1]);
+                            unpack2<T>(rv.y, g4[2], g4[3]);
                         } else {
                             unpack16<float>(rv, g4);
                         }
@@ -408,11 +408,11 @@ conv_fullkw_kernel(const ConvArgs p, const FullkwArgs g) {
                 }
             }
             u128 ov = zero128();
-            if (sizeof(T) == 2) {
-                ov.x = pack_bf16x2(f[0], f[1]);
-                ov.y = pack_bf16x2(f[2], f[3]);
-                f[0] = vt_u2f(ov.x << 16); f[1] = vt_u2f(ov.x & 0xffff0000u);
-                f[2] = vt_u2f(ov.y << 16); f[3] = vt_u2f(ov.y & 0xffff0000u);
+            if constexpr (sizeof(T) == 2) {
+                ov.x = pack2<T>(f[0], f[1]);
+                ov.y = pack2<T>(f[2], f[3]);
+                unpack2<T>(ov.x, f[0], f[1]);
+                unpack2<T>(ov.y, f[2], f[3]);
             } else {
                 ov = pack16<float>(f);
             }

@@ -205,8 +205,6 @@ struct Mma<f32x3_t> {   // on already split operands: (weights head, weights rem
         Mma<bf16_t>::run(acc, wl, ah);
     }
 };
-// bf16 operands: the compute type the specialised kernel families are written for (they pack to bf16 or run bf16 MFMAs inside).
-// fp16 has the generic tile kernels only (ConvArgs of the operator surface, dispatch_generic).
 template <typename T>
 struct is_bf16 {
     static constexpr bool value = false;
@@ -214,6 +212,13 @@ struct is_bf16 {
 template <>
 struct is_bf16<bf16_t> {
     static constexpr bool value = true;
+};
+// 16-bit MFMA operands (bf16 or fp16): the compute types of the specialised kernel families' 16-bit forms.  Wherever such a form
+// rounds inside the kernel (the ToRGB operand, the blur operand of the banded FIR, the z tile of the up-sampling kernels) it
+// rounds to T, and its products run on Mma<T>.
+template <typename T>
+struct is_h16 {
+    static constexpr bool value = std::is_same<T, bf16_t>::value || std::is_same<T, f16_t>::value;
 };
 // 16-bit element type of a conv output that is not fp32 (!out_f32): fp16 for fp16 operands, bf16 for every other compute type
 template <typename T>
@@ -280,7 +285,7 @@ __device__ __forceinline__ void post_act_n(const ConvArgs& p, float* f) {
 
 // Finished values (bias/activation/gain applied) of 8 consecutive output columns n..n+7 of
 // GEMM row m -> NHWC store with the optional residual add and the polyphase pixel shuffle.  OT: the 16-bit output type.
-template <typename OT = bf16_t>
+template <typename OT>
 __device__ __forceinline__ void store_nhwc8(const ConvArgs& p, int m, int n, float* f) {
     const int HoWo = p.Ho * p.Wo;
     int64_t opix = m;
@@ -419,7 +424,7 @@ struct PatchRows {    // 2-D tiles of TW-pixel rows (patch-resident kernel)
 
 // Four consecutive output columns n..n+3 of GEMM row m, finished (bias/activation/gain applied):
 // residual add, pixel shuffle of the polyphase form, NHWC (8/16-byte store) or planar NCHW.  OT: the 16-bit output type.
-template <typename OT = bf16_t>
+template <typename OT>
 __device__ __forceinline__ void store_out4(const ConvArgs& p, int m, int n, float* f) {
     const int HoWo = p.Ho * p.Wo;
     if (p.out_layout == VT_OUT_NHWC) {
@@ -452,32 +457,34 @@ __device__ __forceinline__ void store_out4(const ConvArgs& p, int m, int n, floa
                 for (int i = 0; i < 4; ++i)
                     if (i < nvalid) o[i] = post_act(p, f[i] + (rs ? p.beta * rs[i] : 0.0f));
             }
-        } else if constexpr (!is_bf16<OT>::value) {
+        } else {
             OT* o = (OT*)p.out + opix * p.ld_out + co;
             const OT* rs = p.resid ? (const OT*)p.resid + opix * p.ld_res + co : nullptr;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (i < nvalid) o[i] = from_f32<OT>(post_act(p, f[i] + (rs ? p.beta * to_f32(rs[i]) : 0.0f)));
-        } else {
-            bf16_t* o = (bf16_t*)p.out + opix * p.ld_out + co;
-            const bf16_t* rs = p.resid ? (const bf16_t*)p.resid + opix * p.ld_res + co : nullptr;
             if (p.vec_store && nvalid == 4) {
                 if (rs) {
                     const u64v r = *reinterpret_cast<const u64v*>(rs);
-                    f[0] += p.beta * vt_u2f(r.x << 16);
-                    f[1] += p.beta * vt_u2f(r.x & 0xffff0000u);
-                    f[2] += p.beta * vt_u2f(r.y << 16);
-                    f[3] += p.beta * vt_u2f(r.y & 0xffff0000u);
+                    if constexpr (is_bf16<OT>::value) {   // (the bf16 instances' code as it was tuned)
+                        f[0] += p.beta * vt_u2f(r.x << 16);
+                        f[1] += p.beta * vt_u2f(r.x & 0xffff0000u);
+                        f[2] += p.beta * vt_u2f(r.y << 16);
+                        f[3] += p.beta * vt_u2f(r.y & 0xffff0000u);
+                    } else {
+                        float g[4];
+                        unpack2<OT>(r.x, g[0], g[1]);
+                        unpack2<OT>(r.y, g[2], g[3]);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) f[i] += p.beta * g[i];
+                    }
                 }
                 post_act_n<4>(p, f);
                 u64v v;
-                v.x = pack_bf16x2(f[0], f[1]);
-                v.y = pack_bf16x2(f[2], f[3]);
+                v.x = pack2<OT>(f[0], f[1]);
+                v.y = pack2<OT>(f[2], f[3]);
                 *reinterpret_cast<u64v*>(o) = v;
             } else {
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
-                    if (i < nvalid) o[i] = from_f32<bf16_t>(post_act(p, f[i] + (rs ? p.beta * to_f32(rs[i]) : 0.0f)));
+                    if (i < nvalid) o[i] = from_f32<OT>(post_act(p, f[i] + (rs ? p.beta * to_f32(rs[i]) : 0.0f)));
             }
         }
     } else {
@@ -515,7 +522,7 @@ __device__ __forceinline__ int frag_channel(int b, int q) {  // first of the 4 c
 }
 
 // Eight consecutive output columns n..n+7 of GEMM row m (16-bit NHWC of type OT, vector path): one 16-byte store.
-template <typename OT = bf16_t>
+template <typename OT>
 __device__ __forceinline__ bool store_out8_bf16(const ConvArgs& p, int m, int n, float* f, bool have_rpre = false,
                                                 u128 rpre = u128{0u, 0u, 0u, 0u}) {
     // rpre (have_rpre): the residual vector of this store, fetched by the caller ahead of ALL its stores
@@ -773,7 +780,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x4 (&acc)[BM
             // The weight operand of fragment row a carries its three rows at 4a .. 4a + 2, so the products of the TM <= 4
             // fragment rows land in DIFFERENT rows of one accumulator: lane (q, l15) ends up with the three plane values of
             // pixel l15 of fragment row q -- the reduce-scatter the vector form needed 9 shuffles per plane triple for.
-            constexpr bool RGB_MMA = is_bf16<T>::value;
+            constexpr bool RGB_MMA = is_h16<T>::value;
             static_assert(!RGB_MMA || TM <= 4, "four fragment rows share the 16 rows of the ToRGB accumulator");
             f32x4 racc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -791,7 +798,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x4 (&acc)[BM
                         // weight operand: lane (q, l15) = plane l15 & 3 (row l15 of the operand of fragment row l15 >> 2), channels
                         // nn .. nn + 7 (unconditional load at a clamped address)
                         const bool okw = (l15 & 3) < 3 && nn + 8 <= p.coutT;
-                        const u128 wv = ld128((const bf16_t*)p.rgb_w + (okw ? (l15 & 3) * p.coutT + nn : 0));
+                        const u128 wv = ld128((const T*)p.rgb_w + (okw ? (l15 & 3) * p.coutT + nn : 0));
                         wfrag.x = okw ? wv.x : 0u, wfrag.y = okw ? wv.y : 0u, wfrag.z = okw ? wv.z : 0u, wfrag.w = okw ? wv.w : 0u;
                     } else {
                         rgb_pair_weights<T, PERM>(p, n0 + wn * (TN * 16), b0, q, wq);
@@ -812,7 +819,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x4 (&acc)[BM
                             const bool mine = (l15 >> 2) == a;
                             u128 wa;
                             wa.x = mine ? wfrag.x : 0u, wa.y = mine ? wfrag.y : 0u, wa.z = mine ? wfrag.z : 0u, wa.w = mine ? wfrag.w : 0u;
-                            Mma<bf16_t>::run(racc, wa, pack16<bf16_t>(f));
+                            Mma<T>::run(racc, wa, pack16<T>(f));
                         } else {
 #pragma unroll
                             for (int h = 0; h < 2; ++h)
@@ -1596,7 +1603,7 @@ conv_patch_kernel(const ConvArgs p, const GldsArgs g) {
 template <typename T>
 __global__ void __launch_bounds__(256, 2)   // 2 waves per SIMD = 2 workgroups per CU (<= 256 registers)
 conv3x3_c32_kernel(const ConvArgs p, const GldsArgs g) {
-    static_assert(sizeof(T) == 2, "bf16 only (64-byte pixel rows)");
+    static_assert(is_h16<T>::value, "16-bit operands only (64-byte pixel rows)");
     constexpr int TH = 16, TW = 16, BM = 256, BN = 32, WM = 4, WN = 1;
     constexpr int TM = 4, TN = 2;
     constexpr int PH = TH + 2, PW = TW + 2, PROWS = PH * PW;   // 324 patch pixels
@@ -1668,7 +1675,7 @@ conv3x3_c32_kernel(const ConvArgs p, const GldsArgs g) {
     u128 rwf = u128{0u, 0u, 0u, 0u};
     if (rgbf) {
         const bool okw = (l15 & 3) < 3;
-        const u128 wv = ld128((const bf16_t*)p.rgb_w + (okw ? (l15 & 3) * 32 + q * 8 : 0));
+        const u128 wv = ld128((const T*)p.rgb_w + (okw ? (l15 & 3) * 32 + q * 8 : 0));
         rwf.x = okw ? wv.x : 0u, rwf.y = okw ? wv.y : 0u, rwf.z = okw ? wv.z : 0u, rwf.w = okw ? wv.w : 0u;
     }
     if (p.bias) {
@@ -1762,15 +1769,15 @@ conv3x3_c32_kernel(const ConvArgs p, const GldsArgs g) {
                         f[4 * b + i] = v * ga;
                     }
                 }
-                const u128 fpk = pack16<bf16_t>(f);
+                const u128 fpk = pack16<T>(f);
                 if (rgbf) {
                     const bool mine = (l15 >> 2) == a;
                     u128 wa;
                     wa.x = mine ? rwf.x : 0u, wa.y = mine ? rwf.y : 0u, wa.z = mine ? rwf.z : 0u, wa.w = mine ? rwf.w : 0u;
-                    Mma<bf16_t>::run(racc, wa, fpk);
+                    Mma<T>::run(racc, wa, fpk);
                 }
                 // one 16-byte store per lane: the four lane groups write the pixel's 64 bytes
-                if (m >= 0 && !p.rgb_only) st128((bf16_t*)p.out + (int64_t)m * p.ld_out + cg + q * 8, fpk);
+                if (m >= 0 && !p.rgb_only) st128((T*)p.out + (int64_t)m * p.ld_out + cg + q * 8, fpk);
             }
             if (rgbf) {
                 const float rr[3] = {racc[0], racc[1], racc[2]};   // lane (q, l15): pixel l15 of tile row q
@@ -2024,17 +2031,15 @@ static bool stats_fusable(const ConvArgs& a, int esz) {
 // second pass of the two-pass split-K
 template <typename T>
 static int launch_reduce(const ConvArgs& args, vt_stream stream) {
-    if constexpr (!std::is_same<T, f16_t>::value) {   // (fp16 convs emit no statistics: fill_args)
-        if (stats_fusable(args, (int)sizeof(T))) {
-            const int hw = args.Ho * args.Wo;
-            const int cpx = stat_chunk_pixels(hw);
-            const int chunks = (hw + cpx - 1) / cpx;
-            const int cgroups = vt_cdiv(args.coutT / (16 / (int)sizeof(T)), 16);
-            auto k = conv_splitk_reduce_stats_kernel<T>;
-            VT_LAUNCH(k, dim3((unsigned)(args.N * chunks * cgroups)), dim3(256), stream, args, cpx, chunks, cgroups);
-            g_stats_emitted = true;
-            return vt_check_launch("vt_conv2d(split-K reduce + statistics)");
-        }
+    if (stats_fusable(args, (int)sizeof(T))) {
+        const int hw = args.Ho * args.Wo;
+        const int cpx = stat_chunk_pixels(hw);
+        const int chunks = (hw + cpx - 1) / cpx;
+        const int cgroups = vt_cdiv(args.coutT / (16 / (int)sizeof(T)), 16);
+        auto k = conv_splitk_reduce_stats_kernel<T>;
+        VT_LAUNCH(k, dim3((unsigned)(args.N * chunks * cgroups)), dim3(256), stream, args, cpx, chunks, cgroups);
+        g_stats_emitted = true;
+        return vt_check_launch("vt_conv2d(split-K reduce + statistics)");
     }
     int64_t blocks = ((int64_t)args.M * (args.ldp / 8) + 255) / 256;
     if (blocks > 4096) blocks = 4096;
@@ -2205,7 +2210,7 @@ static bool up_eligible(const ConvArgs& a, GldsArgs& g) {
 
 template <typename T>
 static bool c32_eligible(const ConvArgs& a, GldsArgs& g) {
-    if (!is_bf16<T>::value || a.force_generic || !axes_equal(a) || a.transposed || a.in_scale) return false;
+    if (!is_h16<T>::value || a.force_generic || !axes_equal(a) || a.transposed || a.in_scale) return false;
     if (a.taps != 9 || a.kw != 3 || a.stride != 1 || a.pad != 1 || a.dil != 1) return false;
     if (a.c0 != 32 || a.c1 != 0 || a.cout % 32 != 0 || a.cout > 256 || a.phases != 1 || a.Ho != a.H || a.Wo != a.W) return false;
     if (a.cout != 32 && (a.rgb_w || a.rgb_only)) return false;   // the fused ToRGB needs all channels in one workgroup
@@ -2251,13 +2256,11 @@ template <typename T>
 static TilePlan choose_plan(const ConvArgs& a, int hint, int64_t ws_floats_avail) {
     constexpr int BK = 8 * (16 / (int)sizeof(T));
     constexpr int wg_target = 256;   // workgroups a split-K launch aims for: one per CU
-    // fp16: the generic 1-D tile kernels only (register-staged / direct-to-LDS, split-K); every specialised family is bf16 / fp32
-    constexpr bool FAM = !std::is_same<T, f16_t>::value;
     TilePlan t;
     t.kind = 0;
     t.bm = t.bn = 0;
     t.splitk = 0;
-    if (FAM && a.up_fir) {   // conv_transpose2d + blur: its own kernel family; 16-channel tiles when 32 would leave CUs idle
+    if (a.up_fir) {   // conv_transpose2d + blur: its own kernel family; 16-channel tiles when 32 would leave CUs idle
         t.kind = 5;
         t.bm = 20 * 28;
         const int64_t tiles = (int64_t)vt_cdiv(2 * a.H, 20) * vt_cdiv(2 * a.W, 28);
@@ -2274,7 +2277,7 @@ static TilePlan choose_plan(const ConvArgs& a, int hint, int64_t ws_floats_avail
         // conv_transpose2d(3x3, stride 2) with wide channels: by output parity on the pipelined patch tiles
         // (256 quads x 64 channels x 4 parity classes per workgroup); anything else transposed: the gather form below
         GldsArgs gu;
-        if (FAM && hp != 2 && hbm == 0 && hs == 0 && a.coutT >= 64 && a.cin >= 128 && up_eligible<T>(a, gu)) {
+        if (hp != 2 && hbm == 0 && hs == 0 && a.coutT >= 64 && a.cin >= 128 && up_eligible<T>(a, gu)) {
             t.kind = 1;
             t.bm = 256, t.bn = 64;
             t.splitk = 1;
@@ -2283,7 +2286,7 @@ static TilePlan choose_plan(const ConvArgs& a, int hint, int64_t ws_floats_avail
     }
     {
         // thin outputs (cout <= 3, planar): one launch, K over the wavefronts of a workgroup, no slabs
-        if (FAM && (hp == 6 || (hp == 0 && hbm == 0 && hs == 0)) && thin_eligible<T>(a)) {
+        if ((hp == 6 || (hp == 0 && hbm == 0 && hs == 0)) && thin_eligible<T>(a)) {
             t.kind = 6;
             t.bm = thin16_wanted(a) ? TH16 * TH16 : TH_TW * TH_TW;   // (16 x 16-pixel tiles at the large levels, conv_thin.hpp)
             t.bn = a.taps * a.coutT > 16 ? 32 : 16;
@@ -2297,7 +2300,7 @@ static TilePlan choose_plan(const ConvArgs& a, int hint, int64_t ws_floats_avail
         return (int64_t)vt_cdiv(a.Ho, th) * vt_cdiv(a.Wo, 16) * vt_cdiv(a.coutT, n);
     };
     GldsArgs g;
-    if constexpr (is_bf16<T>::value) {
+    if constexpr (is_h16<T>::value) {
         // stride-2 3x3 convs (the encoder's down-sampling convs) by input parity on patch-resident tiles (conv_patch_s2.hpp):
         // from 128 tiles up -- per IMAGE under VT_BATCH_EXACT (its K order is not the 1-D kernel's, so the choice must then not
         // look at the batch), per launch otherwise (like the other batch-aware plans, section 4.1h of DESIGN.md): the 64^2 ->
@@ -2313,7 +2316,7 @@ static TilePlan choose_plan(const ConvArgs& a, int hint, int64_t ws_floats_avail
             return t;
         }
     }
-    if (FAM && hp != 2 && hbm == 0 && c32_eligible<T>(a, g)) {   // the 1024^2 level: persistent register-weight kernel
+    if (hp != 2 && hbm == 0 && c32_eligible<T>(a, g)) {   // the 1024^2 level: persistent register-weight kernel
         t.kind = 3;
         t.bm = 256;
         t.bn = 32;
@@ -2325,7 +2328,7 @@ static TilePlan choose_plan(const ConvArgs& a, int hint, int64_t ws_floats_avail
         // few pixels per image, wide channels.  Per-image geometry only (batch-invariant like every plan).
         FullkArgs fg;
         const bool hinted = hp == 4;
-        if (FAM && hp != 2 && (hbm == 0 || hinted) && fullk_eligible<T>(a, a.wstream, fg)) {
+        if (hp != 2 && (hbm == 0 || hinted) && fullk_eligible<T>(a, a.wstream, fg)) {
             const int64_t wgs = (int64_t)a.dil * a.dil * fg.tiles_y * fg.tiles_x * vt_cdiv(a.coutT, FK_BN);   // per image
             constexpr int fk_max_wgs = 1024;   // largest per-image grid the heuristic gives the whole-K kernel
             // A batch that fills the GPU with 256-pixel x 128-channel patch tiles (one 8-wave workgroup per CU, no K split) is
@@ -2356,7 +2359,7 @@ static TilePlan choose_plan(const ConvArgs& a, int hint, int64_t ws_floats_avail
             // (round 6: dilation 4 on flat 8 x 8 blocks of its 16 sub-images was built and measured -- 30.3 us against the 29.1 of the
             // weight-stationary kernel, same box, profiles/r06_ab_flat8_c32.txt -- and removed: DESIGN.md 4.1u)
             const bool dil_ok = a.dil == 1 || (a.dil == 2 && !(ppe && ppe[0] == '0') && !a.x3);
-            const bool batch_patch32 = is_bf16<T>::value && !hinted && hbm == 0 && hp == 0 && a.N > 1 && dil_ok && m1 <= 2304 &&
+            const bool batch_patch32 = is_h16<T>::value && !hinted && hbm == 0 && hp == 0 && a.N > 1 && dil_ok && m1 <= 2304 &&
                                        a.coutT >= 128 && !a.tile_stats && !a.in_tile_stats && !a.stats_part &&
                                        (int64_t)a.N * ptiles(16, 32) >= 256 && !batch_exact() && patch_eligible<T>(a, g);
             if (batch_patch32) {
@@ -2390,7 +2393,7 @@ static TilePlan choose_plan(const ConvArgs& a, int hint, int64_t ws_floats_avail
             }
         }
     }
-    const bool can_patch = FAM && hp != 2 && hp != 4 && patch_eligible<T>(a, g);
+    const bool can_patch = hp != 2 && hp != 4 && patch_eligible<T>(a, g);
     int units = 0;  // K units that can be split: K-steps (1-D) or channel chunks (patch)
     if (hbm > 0 && hp != 4) {
         t.kind = hp == 1 ? 1 : 0;
@@ -2527,7 +2530,7 @@ int launch_patch(const ConvArgs& a, const GldsArgs& g, vt_stream stream) {
 // carry nothing else
 template <typename T>
 static bool conv_lean(const ConvArgs& a) {
-    constexpr bool H = is_bf16<T>::value;
+    constexpr bool H = is_h16<T>::value;
     return (a.act == VT_ACT_NONE || a.act == VT_ACT_LRELU) && a.phases == 1 && a.out_layout == VT_OUT_NHWC &&
            (H ? !a.out_f32 : a.out_f32 != 0) && a.vec_store && !a.post_relu && !(a.coutT & 7) &&
            (H ? (!a.resid || !(a.ld_res & 7)) && !(a.ld_out & 7) : !(a.ld_out & 3) && (!a.resid || !(a.ld_res & 3)));
@@ -2670,12 +2673,7 @@ int launch_c32(const ConvArgs& a, const GldsArgs& g, vt_stream stream) {
         const int v = atoi(e);
         if (v > 0 && v < blocks) blocks = v;
     }
-#ifdef VT_EMU
-    auto k = conv3x3_c32_kernel<bf16_t>;
-#else
-    auto k = conv3x3_c32_kernel<bf16_t>;
-#endif
-    (void)sizeof(T);
+    auto k = conv3x3_c32_kernel<T>;
     VT_LAUNCH(k, dim3((unsigned)blocks, (unsigned)groups), dim3(256), stream, args, g);
     return vt_check_launch("vt_conv2d(c32)");
 }
@@ -2713,7 +2711,7 @@ int dispatch(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) 
         const bool db = de ? chunks >= atoi(de) : (chunks >= 4 && (t.bn == 16 || wgs_all <= 768));
         // (single-stage 32-channel forms are capped at 256 registers -- 2 workgroups per CU, a few cold values spilled: 40 vs
         // 51 us and 54 vs 77 us on the 256^2 / 512^2-pixel levels)
-        if constexpr (is_bf16<T>::value) {
+        if constexpr (is_h16<T>::value) {
             // the two top levels (Cin <= 128, >= 128^2 input pixels): one wave per strip, horizontal blur on the matrix cores,
             // no z tile (conv_upblur_rows.hpp).  Other bits than the tile kernels below, so the choice is by shape only.
             if (uprows_wanted<T>(a)) return launch_uprows<T>(a, stream);
@@ -2721,7 +2719,7 @@ int dispatch(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) 
             // The bits of the tile kernels below (same K order, same blur), so the choice may depend on the batch.
             if (upflat_wanted<T>(a)) return launch_upflat<T>(a, stream);
         }
-        if constexpr (is_bf16<T>::value) {
+        if constexpr (is_h16<T>::value) {
             // single-chunk layers (the 1024^2 level) with >= 4 tiles per CU: persistent 8-wave workgroups on 16 x 16-quad tiles
             // -- the 36 KB of weights stay in LDS instead of being re-fetched by every tile (more than the tile's 28 KB
             // patch), the next patch flies during the blur, 8 waves keep the CU as busy as two 4-wave workgroups did.
@@ -2741,7 +2739,7 @@ int dispatch(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) 
             const char* te = getenv("VT_UPBLUR_TALL");
             const int64_t tall_min = te ? atoll(te) : 448;
             const int64_t wgs_tall = (int64_t)a.N * vt_cdiv(2 * a.H, 44) * vt_cdiv(2 * a.W, 28) * vt_cdiv(a.coutT, 32);
-            if constexpr (is_bf16<T>::value) {   // (the fp32 z tile of 47 x 31 pixels does not fit the LDS)
+            if constexpr (is_h16<T>::value) {   // (the fp32 z tile of 47 x 31 pixels does not fit the LDS)
                 if (t.bn == 32 && !db && chunks >= (te ? 2 : 4) && tall_min > 0 && wgs_tall >= tall_min)
                     return launch_upblur<T, 32, 24, 0, 0, 0, 8>(a, stream);
             }
@@ -2765,7 +2763,7 @@ int dispatch(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) 
     if (t.kind == 6) return launch_thin<T>(a, stream);
     if (t.kind == 7) {
         GldsArgs gs;
-        if constexpr (is_bf16<T>::value) {
+        if constexpr (is_h16<T>::value) {
             if (patchs2_eligible<T>(a, gs)) return t.bn == 32 ? launch_patchs2<T, 32>(a, gs, stream) : launch_patchs2<T, 64>(a, gs, stream);
         }
         vt_set_error("vt_conv2d: stride-2 patch kernel requested for an ineligible convolution");
@@ -2793,7 +2791,7 @@ int dispatch(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) 
             vt_set_error("vt_conv2d: c32 kernel requested for an ineligible convolution");
             return VT_ERR_UNSUPPORTED;
         }
-        return launch_c32<T>(a, g, stream);
+        if constexpr (is_h16<T>::value) return launch_c32<T>(a, g, stream);   // (c32_eligible admits 16-bit operands only)
     }
     if (t.kind == 1 && a.transposed) {
         GldsArgs g;
@@ -2825,7 +2823,7 @@ int dispatch(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) 
             const bool pipe = !(e && e[0] == '0') && !a.x3;
             // one chunk of K, one channel tile, several tiles per CU: weights resident, persistent workgroups (VT_PATCH_PIPE=1:
             // the plain pipelined form, A/B)
-            if constexpr (is_bf16<T>::value) {
+            if constexpr (is_h16<T>::value) {
                 // (lean epilogue: bf16 NHWC vector stores of all 64 channels, bias + (Leaky)ReLU * gain, optional fused ToRGB)
                 const bool lean = a.coutT == 64 && a.phases == 1 && a.out_layout == VT_OUT_NHWC && !a.out_f32 && a.vec_store &&
                                   a.ld_out % 8 == 0 && !a.resid && !a.slope_vec && !a.alpha_dev && !a.post_relu && !a.stats_part &&
@@ -2839,7 +2837,7 @@ int dispatch(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) 
             }
             // more tiles than CUs, whole K, lean epilogue: persistent workgroups, the pipeline runs across tile boundaries
             // (VT_PATCH_PIPE=1: one workgroup per tile, A/B).  VT_BATCH_EXACT or not: the same bits either way.
-            if constexpr (is_bf16<T>::value) {
+            if constexpr (is_h16<T>::value) {
                 if (pipe && !(e && e[0] == '1') && a.dil == 1 && t.bm == 256 && (t.bn == 128 || t.bn == 64) && a.splitk <= 1 &&
                     conv_lean<T>(a) && vt_cdiv(a.coutT, t.bn) * t.bn * 8 <= PQ_TAB_BYTES &&   // (the tables of every channel tile, conv_patch_persist.hpp)
                     (int64_t)a.N * vt_cdiv(a.Ho, 16) * vt_cdiv(a.Wo, 16) * vt_cdiv(a.coutT, t.bn) > patchw_wgs()) {
@@ -2851,7 +2849,7 @@ int dispatch(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) 
             if (pipe && a.dil == 1 && t.bm == 256 && t.bn == 64) return launch_patchp<T, 16, 64, 4, 2, 4>(a, g, stream);
             // 32-channel tiles: all nine taps of a chunk resident, one barrier per chunk (conv_patch_chunk.hpp; VT_PATCH_PIPE=1:
             // the tap-granular pipeline, A/B -- same bits)
-            if constexpr (is_bf16<T>::value) {
+            if constexpr (is_h16<T>::value) {
                 if (pipe && !(e && e[0] == '1') && a.dil == 1 && t.bm == 256 && t.bn == 32) return launch_patchc<T>(a, g, stream);
                 if (pipe && !(e && e[0] == '1') && a.dil == 2 && t.bm == 256 && t.bn == 32 && !a.stats_part)
                     return launch_patchc<T, 2>(a, g, stream);
@@ -2889,35 +2887,13 @@ int dispatch(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) 
     return VT_ERR_UNSUPPORTED;
 }
 
-// fp16 operands (the operator surface, vtoonify_amd/op): the generic 1-D tile kernels -- register-staged, or direct-to-LDS where
-// glds_eligible holds -- with split-K, fp16 NHWC or fp32 NCHW outputs.  No specialised family has an fp16 instance.
+// the up-sampling form dispatch<T> runs for a kind-5 plan: 9 = the strip-marching form of the top levels (conv_upblur_rows.hpp),
+// 10 = the flat tiles of the deep ones (conv_upblur_flat.hpp), else the tile kernels (vt_conv2d_tile)
 template <typename T>
-int dispatch_generic(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) {
-    ConvArgs a = a0;
-    a.force_generic = hint >= 1000000000 || !axes_equal(a);
-    if (a.up_fir || a.rgb_w || a.rgb_only || a.in_absdiff || a.stats_part || a.tile_stats || a.in_tile_stats) {
-        vt_set_error("vt_conv2d: fp16 runs the generic tile kernels only (no up_fir, fused ToRGB, in_absdiff or statistics forms)");
-        return VT_ERR_UNSUPPORTED;
-    }
-    const TilePlan t = choose_plan<T>(a, hint % 1000000000, ws_floats);
-    if (t.kind != 0) {
-        vt_set_error("vt_conv2d: plan kind %d has no fp16 instance (fp16 runs the generic tile kernels only)", t.kind);
-        return VT_ERR_UNSUPPORTED;
-    }
-    a.splitk = t.splitk;
-    a.ldp = slab_ld(a.coutT);
-    const int bm = t.bm, bn = t.bn;
-#define VT_CFG(M_, N_, WM_, WN_) \
-    if (bm == M_ && bn == N_) return launch_cfg<T, M_, N_, WM_, WN_>(a, stream);
-    VT_CFG(128, 128, 2, 2)
-    VT_CFG(128, 64, 2, 2)
-    VT_CFG(128, 32, 4, 1)
-    VT_CFG(128, 16, 4, 1)
-    VT_CFG(64, 64, 2, 2)
-    VT_CFG(64, 128, 2, 2)
-#undef VT_CFG
-    vt_set_error("vt_conv2d: no compiled fp16 tile %dx%d", bm, bn);
-    return VT_ERR_UNSUPPORTED;
+static void upblur_form(const ConvArgs& a, int& kind, int& bm, int& bn) {
+    UpblurArgs ub;
+    if (uprows_wanted<T>(a) && upblur_eligible<T>(a, ub, 2, UR_OW)) kind = 9, bm = UR_OW, bn = 32;
+    else if (upflat_wanted<T>(a) && upblur_eligible<T>(a, ub, 16, 64)) kind = 10, bm = 10 * UF_PW, bn = upflat_cn(a);
 }
 
 // the plan of a descriptor's compute dtype (vt_conv2d_tile / _splitk_mode / _ws_bytes)
@@ -2960,7 +2936,7 @@ static int fill_args(const vt_conv_desc* d, ConvArgs& a) {
                "vt_conv2d: tensor too large for 32-bit pixel indices");
 
     VT_REQUIRE(!d->stats_part || (d->phases == 1 && d->out_layout == VT_OUT_NHWC && d->out_dtype == cdt &&
-                                  d->cout % 8 == 0 && (cdt == VT_BF16 || cdt == VT_F32)),
+                                  d->cout % 8 == 0),
                "vt_conv2d: stats_part needs phases == 1, NHWC output in the compute dtype, cout %% 8 == 0");
     VT_REQUIRE(!d->post_relu || !d->rgb_weight, "vt_conv2d: post_relu cannot be combined with the fused ToRGB");
     VT_REQUIRE(!d->rgb_weight || (d->rgb_out && d->phases == 1 && d->out_layout == VT_OUT_NHWC && !d->transposed),
@@ -3044,7 +3020,7 @@ extern "C" int vt_conv2d(const vt_conv_desc* d, vt_stream stream) {
     const int64_t wsf = (d->splitk_ws && d->splitk_ws_bytes > VT_TICKET_BYTES) ? (d->splitk_ws_bytes - VT_TICKET_BYTES) / 4 : 0;
     g_stats_emitted = false;
     a.x3 = d->dtype == VT_F32X3;
-    const int rcl = d->dtype == VT_F16    ? dispatch_generic<f16_t>(a, d->tile_hint, wsf, stream)
+    const int rcl = d->dtype == VT_F16    ? dispatch<f16_t>(a, d->tile_hint, wsf, stream)
                     : d->dtype == VT_BF16 ? dispatch<bf16_t>(a, d->tile_hint, wsf, stream)
                                           : dispatch<float>(a, d->tile_hint, wsf, stream);
     if (rcl != VT_OK || !a.stats_part || g_stats_emitted || d->splitk_phase == 1) return rcl;
@@ -3068,11 +3044,8 @@ extern "C" int vt_conv2d_tile(const vt_conv_desc* d) {
         kind = glds ? 2 : 0;
     }
     int bm = t.bm, bn = t.bn;
-    if (kind == 5 && d->dtype == VT_BF16) {   // 9 = the strip-marching form of the top up-sampling convs (conv_upblur_rows.hpp)
-        UpblurArgs ub;
-        if (uprows_wanted<bf16_t>(a) && upblur_eligible<bf16_t>(a, ub, 2, UR_OW)) kind = 9, bm = UR_OW, bn = 32;
-        else if (upflat_wanted<bf16_t>(a) && upblur_eligible<bf16_t>(a, ub, 16, 64)) kind = 10, bm = 10 * UF_PW, bn = upflat_cn(a);   // conv_upblur_flat.hpp
-    }
+    if (kind == 5 && d->dtype == VT_BF16) upblur_form<bf16_t>(a, kind, bm, bn);
+    if (kind == 5 && d->dtype == VT_F16) upblur_form<f16_t>(a, kind, bm, bn);
     return kind * 100000000 + t.splitk * 1000000 + bm * 1000 + bn;
 }
 
@@ -3102,7 +3075,7 @@ extern "C" int64_t vt_conv2d_ws_bytes(const vt_conv_desc* d) {
 }
 
 extern "C" int64_t vt_conv_weight_stream_bytes(int cout, int taps, int cin, int dtype) {
-    if (cout <= 0 || taps <= 0 || cin <= 0 || (dtype != VT_F32 && dtype != VT_BF16)) return -1;
+    if (cout <= 0 || taps <= 0 || cin <= 0 || (dtype != VT_F32 && dtype != VT_BF16 && dtype != VT_F16)) return -1;
     const int esz = dtype == VT_F32 ? 4 : 2;
     const int bk = 128 / esz;
     if (cin % bk != 0) return -1;
@@ -3128,6 +3101,9 @@ extern "C" int vt_conv_weight_stream(void* out, const void* packed, int cout, in
     if (dtype == VT_BF16) {
         auto k = weight_stream_kernel<bf16_t>;
         VT_LAUNCH(k, dim3((unsigned)blocks), dim3(256), stream, (bf16_t*)out, (const bf16_t*)packed, cout, taps, cin, total16);
+    } else if (dtype == VT_F16) {
+        auto k = weight_stream_kernel<f16_t>;
+        VT_LAUNCH(k, dim3((unsigned)blocks), dim3(256), stream, (f16_t*)out, (const f16_t*)packed, cout, taps, cin, total16);
     } else {
         auto k = weight_stream_kernel<float>;
         VT_LAUNCH(k, dim3((unsigned)blocks), dim3(256), stream, (float*)out, (const float*)packed, cout, taps, cin, total16);

@@ -229,7 +229,7 @@ conv_patchw_kernel(const ConvArgs p, const GldsArgs g) {
                     const int pl = (l15 & 3) < 3 ? (l15 & 3) : 0;
                     float wv[8];
                     unpack16<float>(ld128(tab + (1 + pl) * BN + c0), wv), unpack16<float>(ld128(tab + (1 + pl) * BN + c0 + 4), wv + 4);
-                    const u128 wp = pack16<bf16_t>(wv);
+                    const u128 wp = pack16<T>(wv);
                     const bool okw = (l15 & 3) < 3;
                     wfrag.x = okw ? wp.x : 0u, wfrag.y = okw ? wp.y : 0u, wfrag.z = okw ? wp.z : 0u, wfrag.w = okw ? wp.w : 0u;
                 }
@@ -248,7 +248,7 @@ conv_patchw_kernel(const ConvArgs p, const GldsArgs g) {
                         const bool mine = (l15 >> 2) == a;
                         u128 wa;
                         wa.x = mine ? wfrag.x : 0u, wa.y = mine ? wfrag.y : 0u, wa.z = mine ? wfrag.z : 0u, wa.w = mine ? wfrag.w : 0u;
-                        Mma<bf16_t>::run(racc, wa, fpk);
+                        Mma<T>::run(racc, wa, fpk);
                     }
                     vt_bstore_hidden<4>(rout, m >= 0 ? (uint32_t)(m * p.ld_out + c0) * (uint32_t)ESZ : GLDS_OOB, fpk);
                 }

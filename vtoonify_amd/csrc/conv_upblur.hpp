@@ -316,10 +316,10 @@ conv_upblur_kernel(const ConvArgs p, const UpblurArgs g) {
                     const int b0 = subp * PXB + ch * ESZ;                   // byte offset inside the line
                     const int phys = ((b0 >> 4) ^ (line & 7)) << 4;
                     float f[4] = {acc[c][m][n][0], acc[c][m][n][1], acc[c][m][n][2], acc[c][m][n][3]};
-                    if (ESZ == 2) {
+                    if constexpr (ESZ == 2) {
                         u64v v;
-                        v.x = pack_bf16x2(f[0], f[1]);
-                        v.y = pack_bf16x2(f[2], f[3]);
+                        v.x = pack2<T>(f[0], f[1]);
+                        v.y = pack2<T>(f[2], f[3]);
                         *reinterpret_cast<u64v*>(zl + phys + (b0 & 15)) = v;
                     } else {
                         st128(zl + phys, pack16<float>(f));

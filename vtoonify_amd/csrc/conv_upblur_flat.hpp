@@ -201,8 +201,8 @@ conv_upflat_kernel(const ConvArgs p, const UpblurArgs g) {
                 const int b0 = subp * PXB + ch * ESZ;                   // byte offset inside the line
                 const int phys = ((b0 >> 4) ^ (line & 7)) << 4;
                 u64v v;
-                v.x = pack_bf16x2(acc[cl][m][n][0], acc[cl][m][n][1]);
-                v.y = pack_bf16x2(acc[cl][m][n][2], acc[cl][m][n][3]);
+                v.x = pack2<T>(acc[cl][m][n][0], acc[cl][m][n][1]);
+                v.y = pack2<T>(acc[cl][m][n][2], acc[cl][m][n][3]);
                 *reinterpret_cast<u64v*>(zl + phys + (b0 & 15)) = v;
             }
         }

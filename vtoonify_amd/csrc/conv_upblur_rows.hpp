@@ -1,4 +1,4 @@
-// Up-sampling StyledConv of the two top levels (Cin = 64 / 128, bf16) with the blur ON THE MATRIX CORES: conv_transpose2d(3x3,
+// Up-sampling StyledConv of the two top levels (Cin = 64 / 128, bf16 or fp16) with the blur ON THE MATRIX CORES: conv_transpose2d(3x3,
 // stride 2) + 4x4 FIR + bias + LeakyReLU (model/stylegan/model.py:273-286, 74-90, 364-370) without the z tile ever visiting LDS.
 // Included by conv_igemm.hip inside its anonymous namespace (round 5).
 //
@@ -12,7 +12,7 @@
 //      weights out of LDS (all 9 taps x 32 output channels resident for the life of the workgroup).  Four accumulator sets =
 //      the parity classes (pa, pb): z[2y + pa][2x + pb]; a lane (q, l15) ends with pixels 4q..4q+3 of channel l15.
 //   2. the blur, BOTH directions, as MFMAs on the finished accumulators: the lane's 8 values of a z row (both column parities of
-//      its 4 pixels = the 8 z columns 8q..8q+7 of the strip, rounded to bf16 like the z tile of conv_upblur.hpp) ARE the A
+//      its 4 pixels = the 8 z columns 8q..8q+7 of the strip, rounded to the compute type like the z tile of conv_upblur.hpp) ARE the A
 //      operand of a product with a constant banded matrix (B operand: FIR row a spread on the band of output column o), and
 //      the accumulator is the running sum of the output row the z row feeds with FIR row a:
 //          out[Y][c][o] = sum_a sum_j z[Y-1+a][c][j] K[a][j-o-1]        (4 MFMAs per output row and 16 columns, one per z row)
@@ -53,9 +53,9 @@ struct UprowsArgs {
 
 constexpr int UR_OW = 28;   // output columns per strip
 
-template <int CIN>
+template <typename T, int CIN>
 __global__ void __launch_bounds__(512, 1) conv_upblur_rows_kernel(const ConvArgs p, const UprowsArgs g) {
-    using T = bf16_t;
+    static_assert(is_h16<T>::value, "16-bit MFMA operands");
     constexpr int ESZ = 2, BK = 64, CN = 32, TN = 2, NW = 8;
     constexpr int KS = CIN / 32;                     // MFMA K-steps per tap
     constexpr int NCH = CIN / BK;                    // 128-byte chunks of a weight row
@@ -100,8 +100,8 @@ __global__ void __launch_bounds__(512, 1) conv_upblur_rows_kernel(const ConvArgs
 
     // ---- constants of the wave: the blur matrix, bias / activation of the lane's 8 channels -----------------------------
     float bv[8], gneg[8], ga;
-    // B operands of the blur: tk[a][nb] = the band of FIR row a for output columns 16 nb .. 16 nb + 15 of the strip (bf16 heads;
-    // tr: the remainders, used only when some tap is not a bf16 number -- [1,3,3,1]-type kernels are exact)
+    // B operands of the blur: tk[a][nb] = the band of FIR row a for output columns 16 nb .. 16 nb + 15 of the strip (heads rounded
+    // to T; tr: the remainders, used only when some tap is not a T number -- [1,3,3,1]-type kernels are exact in bf16 and fp16)
     u128 tk[2][2];              // FIR rows 0 (= 3) and 1 (= 2) of the fast form
     bool fast;                  // exact taps, FIR rows 0 = 3 and 1 = 2, one activation slope: the copy of the loop without remainder bands,
                                 // with two bands and a scalar slope (24 registers less)
@@ -131,7 +131,8 @@ __global__ void __launch_bounds__(512, 1) conv_upblur_rows_kernel(const ConvArgs
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const float tap = ky[a] * kx[i];
-                exact = exact && (bf16_bits_to_f32(f32_to_bf16_bits(tap)) == tap);
+                if constexpr (is_bf16<T>::value) exact = exact && (bf16_bits_to_f32(f32_to_bf16_bits(tap)) == tap);
+                else exact = exact && (to_f32(from_f32<T>(tap)) == tap);
             }
         ga = p.gain_alpha * (p.alpha_dev ? p.alpha_dev[0] : 1.0f);
         // lane's channels: fragment n, element e <-> channel n0 + 8q + 4n + e (frag_channel<true>)
@@ -446,10 +447,10 @@ int launch_uprows(const ConvArgs& a, vt_stream stream) {
     const int blocks = slots * args.tiles_n;
     g.xcd_group = (slots % 8 == 0) ? 1 : 0;
     if (a.cin == 64) {
-        auto k = conv_upblur_rows_kernel<64>;
+        auto k = conv_upblur_rows_kernel<T, 64>;
         VT_LAUNCH(k, dim3((unsigned)blocks), dim3(512), stream, args, g);
     } else {
-        auto k = conv_upblur_rows_kernel<128>;
+        auto k = conv_upblur_rows_kernel<T, 128>;
         VT_LAUNCH(k, dim3((unsigned)blocks), dim3(512), stream, args, g);
     }
     return vt_check_launch("vt_conv2d(upblur rows)");

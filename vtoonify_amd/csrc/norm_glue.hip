@@ -732,7 +732,7 @@ extern "C" int vt_instnorm_stats(float* scale, float* shift, const void* x, int 
                                  vt_stream stream) {
     VT_REQUIRE(scale && shift && x && partials, "vt_instnorm_stats: null tensor");
     VT_REQUIRE(n > 0 && hw > 0 && c > 0 && c % 16 == 0, "vt_instnorm_stats: c must be a positive multiple of 16");
-    VT_REQUIRE(dtype == VT_F32 || dtype == VT_BF16, "vt_instnorm_stats: dtype");
+    VT_REQUIRE(dtype == VT_F32 || dtype == VT_BF16 || dtype == VT_F16, "vt_instnorm_stats: dtype");
     const int cpx = stat_chunk_pixels(hw);
     const int chunks = (hw + cpx - 1) / cpx;
     const int ctot = absdiff_other ? 2 * c : c;
@@ -745,8 +745,10 @@ extern "C" int vt_instnorm_stats(float* scale, float* shift, const void* x, int 
     }
     if (dtype == VT_F32) {
         if (absdiff_other) VT_IN_LAUNCH(float, true) else VT_IN_LAUNCH(float, false)
-    } else {
+    } else if (dtype == VT_BF16) {
         if (absdiff_other) VT_IN_LAUNCH(bf16_t, true) else VT_IN_LAUNCH(bf16_t, false)
+    } else {
+        if (absdiff_other) VT_IN_LAUNCH(f16_t, true) else VT_IN_LAUNCH(f16_t, false)
     }
 #undef VT_IN_LAUNCH
     int rc = vt_check_launch("vt_instnorm_stats(partial)");
@@ -773,6 +775,11 @@ extern "C" int vt_affine_apply(void* out, int ld_out, const void* x, int ld_x,
         auto k = affine_apply_kernel<bf16_t>;
         VT_LAUNCH(k, dim3(grid_for(total)), dim3(256), stream, (bf16_t*)out, ld_out, (const bf16_t*)x, ld_x,
                   (const bf16_t*)absdiff_other, ld_other, scale, shift, n, hw, c);
+    } else if (dtype == VT_F16) {
+        const int64_t total = (int64_t)n * hw * (c / 8) * halves;
+        auto k = affine_apply_kernel<f16_t>;
+        VT_LAUNCH(k, dim3(grid_for(total)), dim3(256), stream, (f16_t*)out, ld_out, (const f16_t*)x, ld_x,
+                  (const f16_t*)absdiff_other, ld_other, scale, shift, n, hw, c);
     } else {
         vt_set_error("vt_affine_apply: dtype");
         return VT_ERR_UNSUPPORTED;
@@ -795,6 +802,11 @@ extern "C" int vt_fusion_pack(void* out, int ld_out, const void* f_e, int ld_e, 
         auto k = fusion_pack_kernel<bf16_t>;
         VT_LAUNCH(k, dim3(grid_for(total)), dim3(256), stream, (bf16_t*)out, ld_out, (const bf16_t*)f_e, ld_e,
                   mask, skip, n, hw, c);
+    } else if (dtype == VT_F16) {
+        const int64_t total = (int64_t)n * hw * (ld_out / 8);
+        auto k = fusion_pack_kernel<f16_t>;
+        VT_LAUNCH(k, dim3(grid_for(total)), dim3(256), stream, (f16_t*)out, ld_out, (const f16_t*)f_e, ld_e,
+                  mask, skip, n, hw, c);
     } else {
         vt_set_error("vt_fusion_pack: dtype");
         return VT_ERR_UNSUPPORTED;
@@ -809,7 +821,7 @@ static int nchw_to_nhwc_out(void* out, int ld_out, const TI* in, int n, int c, i
     const int64_t total = (int64_t)n * (cpad / 8) * hw;
     // one thread per pixel for the narrow tensors of the model boundary (16-byte aligned pixel rows)
     const int osz = out_dtype == VT_F32 ? 4 : 2;
-    if ((cpad == 8 || cpad == 16 || cpad == 24 || cpad == 32) && (out_dtype == VT_F32 || out_dtype == VT_BF16) &&
+    if ((cpad == 8 || cpad == 16 || cpad == 24 || cpad == 32) && (out_dtype == VT_F32 || out_dtype == VT_BF16 || out_dtype == VT_F16) &&
         ((int64_t)ld_out * osz) % 16 == 0 && (uintptr_t)out % 16 == 0) {
         const unsigned grid = grid_for((int64_t)n * hw);
 #define VT_PIX(TO_, CP_)                                                                                        \
@@ -819,7 +831,7 @@ static int nchw_to_nhwc_out(void* out, int ld_out, const TI* in, int n, int c, i
     }
 #define VT_PIX_C(TO_) \
     if (cpad == 8) VT_PIX(TO_, 8) else if (cpad == 16) VT_PIX(TO_, 16) else if (cpad == 24) VT_PIX(TO_, 24) else VT_PIX(TO_, 32)
-        if (out_dtype == VT_F32) { VT_PIX_C(float) } else { VT_PIX_C(bf16_t) }
+        if (out_dtype == VT_F32) { VT_PIX_C(float) } else if (out_dtype == VT_BF16) { VT_PIX_C(bf16_t) } else { VT_PIX_C(f16_t) }
 #undef VT_PIX_C
 #undef VT_PIX
         return vt_check_launch("vt_nchw_to_nhwc");
@@ -981,9 +993,12 @@ int vt_internal_instnorm_partial(void* partials, const void* x, int ld_x, int n,
     if (dtype == VT_F32) {
         auto k = instnorm_partial_kernel<float, false>;
         VT_LAUNCH(k, grid, block, stream, (StatRec*)partials, (const float*)x, ld_x, (const float*)nullptr, 0, hw, c, cpx, chunks);
-    } else {
+    } else if (dtype == VT_BF16) {
         auto k = instnorm_partial_kernel<bf16_t, false>;
         VT_LAUNCH(k, grid, block, stream, (StatRec*)partials, (const bf16_t*)x, ld_x, (const bf16_t*)nullptr, 0, hw, c, cpx, chunks);
+    } else {
+        auto k = instnorm_partial_kernel<f16_t, false>;
+        VT_LAUNCH(k, grid, block, stream, (StatRec*)partials, (const f16_t*)x, ld_x, (const f16_t*)nullptr, 0, hw, c, cpx, chunks);
     }
     return vt_check_launch("instnorm statistics");
 }
@@ -995,7 +1010,7 @@ extern "C" int vt_instnorm_apply_stats(void* out, int ld_out, const void* x, int
                                        vt_stream stream) {
     VT_REQUIRE(out && x && partials, "vt_instnorm_apply_stats: null tensor");
     VT_REQUIRE(n > 0 && hw > 0 && c > 0 && c % 16 == 0, "vt_instnorm_apply_stats: c must be a positive multiple of 16");
-    VT_REQUIRE(dtype == VT_F32 || dtype == VT_BF16, "vt_instnorm_apply_stats: dtype");
+    VT_REQUIRE(dtype == VT_F32 || dtype == VT_BF16 || dtype == VT_F16, "vt_instnorm_apply_stats: dtype");
     if ((int64_t)hw > 16384) {
         vt_set_error("vt_instnorm_apply_stats: tensor too large for the fused form");
         return VT_ERR_UNSUPPORTED;
@@ -1007,9 +1022,13 @@ extern "C" int vt_instnorm_apply_stats(void* out, int ld_out, const void* x, int
         auto k = instnorm_apply_small_kernel<float>;
         VT_LAUNCH(k, dim3(nblk), dim3(256), stream, (float*)out, ld_out, (const float*)x, ld_x,
                   (const StatRec*)partials, hw, c, cpx, chunks, style_gb, ld_gb);
-    } else {
+    } else if (dtype == VT_BF16) {
         auto k = instnorm_apply_small_kernel<bf16_t>;
         VT_LAUNCH(k, dim3(nblk), dim3(256), stream, (bf16_t*)out, ld_out, (const bf16_t*)x, ld_x,
+                  (const StatRec*)partials, hw, c, cpx, chunks, style_gb, ld_gb);
+    } else {
+        auto k = instnorm_apply_small_kernel<f16_t>;
+        VT_LAUNCH(k, dim3(nblk), dim3(256), stream, (f16_t*)out, ld_out, (const f16_t*)x, ld_x,
                   (const StatRec*)partials, hw, c, cpx, chunks, style_gb, ld_gb);
     }
     return vt_check_launch("vt_instnorm_apply_stats");
@@ -1020,7 +1039,7 @@ extern "C" int vt_instnorm_plane(void* out, int ld_out, const void* x, int ld_x,
                                  int n, int hw, int c, const float* style_gb, int ld_gb, int dtype, vt_stream stream) {
     VT_REQUIRE(out && x, "vt_instnorm_plane: null tensor");
     VT_REQUIRE(n > 0 && hw > 0 && c > 0 && c % 8 == 0, "vt_instnorm_plane: c must be a positive multiple of 8");
-    VT_REQUIRE(dtype == VT_F32 || dtype == VT_BF16, "vt_instnorm_plane: dtype");
+    VT_REQUIRE(dtype == VT_F32 || dtype == VT_BF16 || dtype == VT_F16, "vt_instnorm_plane: dtype");
     VT_REQUIRE(!absdiff_other || out != x, "vt_instnorm_plane: the cat[x, |x - other|] form cannot run in place");
     if (hw > 4096) {
         vt_set_error("vt_instnorm_plane: plane too large for the register-resident form (hw <= 4096)");
@@ -1045,8 +1064,10 @@ extern "C" int vt_instnorm_plane(void* out, int ld_out, const void* x, int ld_x,
     else if (vpw == 2) VT_PLANE(TT, 16, 2, HO_) else VT_PLANE(TT, 16, 1, HO_)
     if (dtype == VT_F32) {
         if (absdiff_other) { VT_PLANE_P(float, true) } else { VT_PLANE_P(float, false) }
-    } else {
+    } else if (dtype == VT_BF16) {
         if (absdiff_other) { VT_PLANE_P(bf16_t, true) } else { VT_PLANE_P(bf16_t, false) }
+    } else {
+        if (absdiff_other) { VT_PLANE_P(f16_t, true) } else { VT_PLANE_P(f16_t, false) }
     }
 #undef VT_PLANE_P
 #undef VT_PLANE
@@ -1061,7 +1082,7 @@ extern "C" int vt_instnorm_apply(void* out, int ld_out, const void* x, int ld_x,
                                  vt_stream stream) {
     VT_REQUIRE(out && x && partials, "vt_instnorm_apply: null tensor");
     VT_REQUIRE(n > 0 && hw > 0 && c > 0 && c % 16 == 0, "vt_instnorm_apply: c must be a positive multiple of 16");
-    VT_REQUIRE(dtype == VT_F32 || dtype == VT_BF16, "vt_instnorm_apply: dtype");
+    VT_REQUIRE(dtype == VT_F32 || dtype == VT_BF16 || dtype == VT_F16, "vt_instnorm_apply: dtype");
     const int cpx = stat_chunk_pixels(hw);
     const int chunks = (hw + cpx - 1) / cpx;
     if ((int64_t)hw > 16384) {   // one workgroup walks a whole plane: small planes only
@@ -1072,9 +1093,12 @@ extern "C" int vt_instnorm_apply(void* out, int ld_out, const void* x, int ld_x,
     if (dtype == VT_F32) {
         auto k = instnorm_partial_kernel<float, false>;
         VT_LAUNCH(k, grid, block, stream, (StatRec*)partials, (const float*)x, ld_x, (const float*)nullptr, 0, hw, c, cpx, chunks);
-    } else {
+    } else if (dtype == VT_BF16) {
         auto k = instnorm_partial_kernel<bf16_t, false>;
         VT_LAUNCH(k, grid, block, stream, (StatRec*)partials, (const bf16_t*)x, ld_x, (const bf16_t*)nullptr, 0, hw, c, cpx, chunks);
+    } else {
+        auto k = instnorm_partial_kernel<f16_t, false>;
+        VT_LAUNCH(k, grid, block, stream, (StatRec*)partials, (const f16_t*)x, ld_x, (const f16_t*)nullptr, 0, hw, c, cpx, chunks);
     }
     int rc = vt_check_launch("vt_instnorm_apply(partial)");
     if (rc) return rc;
@@ -1083,9 +1107,13 @@ extern "C" int vt_instnorm_apply(void* out, int ld_out, const void* x, int ld_x,
         auto k = instnorm_apply_small_kernel<float>;
         VT_LAUNCH(k, dim3(nblk), block, stream, (float*)out, ld_out, (const float*)x, ld_x,
                   (const StatRec*)partials, hw, c, cpx, chunks, style_gb, ld_gb);
-    } else {
+    } else if (dtype == VT_BF16) {
         auto k = instnorm_apply_small_kernel<bf16_t>;
         VT_LAUNCH(k, dim3(nblk), block, stream, (bf16_t*)out, ld_out, (const bf16_t*)x, ld_x,
+                  (const StatRec*)partials, hw, c, cpx, chunks, style_gb, ld_gb);
+    } else {
+        auto k = instnorm_apply_small_kernel<f16_t>;
+        VT_LAUNCH(k, dim3(nblk), block, stream, (f16_t*)out, ld_out, (const f16_t*)x, ld_x,
                   (const StatRec*)partials, hw, c, cpx, chunks, style_gb, ld_gb);
     }
     return vt_check_launch("vt_instnorm_apply");

@@ -377,6 +377,9 @@ extern "C" int vt_modulate_weight(void* out, const float* weight, const float* s
     } else if (out_dtype == VT_BF16) {
         auto kf = modulate_weight_kernel<bf16_t>;
         VT_LAUNCH(kf, grid, block, stream, (bf16_t*)out, weight, s, cout, cin, k, scale, demodulate, fir);
+    } else if (out_dtype == VT_F16) {
+        auto kf = modulate_weight_kernel<f16_t>;
+        VT_LAUNCH(kf, grid, block, stream, (f16_t*)out, weight, s, cout, cin, k, scale, demodulate, fir);
     } else {
         vt_set_error("vt_modulate_weight: unsupported dtype %d", out_dtype);
         return VT_ERR_UNSUPPORTED;
@@ -455,7 +458,7 @@ extern "C" int vt_modulate_weight_batch_gated(const vt_modulate_item* items, int
 }
 static int modulate_batch_impl(const vt_modulate_item* items, int n_items, int out_dtype, const int* gate, vt_stream stream) {
     VT_REQUIRE(items && n_items >= 0, "vt_modulate_weight_batch: bad arguments");
-    VT_REQUIRE(out_dtype == VT_F32 || out_dtype == VT_BF16, "vt_modulate_weight_batch: unsupported dtype %d", out_dtype);
+    VT_REQUIRE(out_dtype == VT_F32 || out_dtype == VT_BF16 || out_dtype == VT_F16, "vt_modulate_weight_batch: unsupported dtype %d", out_dtype);
     for (int base = 0; base < n_items; base += MOD_BATCH) {
         ModTable t;
         memset(&t, 0, sizeof(t));
@@ -476,8 +479,11 @@ static int modulate_batch_impl(const vt_modulate_item* items, int n_items, int o
         if (out_dtype == VT_F32) {
             auto kf = modulate_batch_kernel<float>;
             VT_LAUNCH(kf, dim3((unsigned)rows), dim3(256), stream, t);
-        } else {
+        } else if (out_dtype == VT_BF16) {
             auto kf = modulate_batch_kernel<bf16_t>;
+            VT_LAUNCH(kf, dim3((unsigned)rows), dim3(256), stream, t);
+        } else {
+            auto kf = modulate_batch_kernel<f16_t>;
             VT_LAUNCH(kf, dim3((unsigned)rows), dim3(256), stream, t);
         }
         const int rc = vt_check_launch("vt_modulate_weight_batch");

@@ -219,14 +219,51 @@ __device__ __forceinline__ u128 pack16<bf16_t>(const float* f) {
     v.w = pack_bf16x2(f[6], f[7]);
     return v;
 }
+// two fp32 -> packed fp16 pair, round-to-nearest-even (one v_cvt_pk_f16_f32 on gfx950)
+__device__ __forceinline__ uint32_t pack_f16x2(float lo, float hi) {
+#ifdef VT_EMU
+    return (uint32_t)emu_float_to_half(lo) | ((uint32_t)emu_float_to_half(hi) << 16);
+#else
+    typedef _Float16 vt_f16x2 __attribute__((ext_vector_type(2)));
+    typedef float vt_f32x2 __attribute__((ext_vector_type(2)));
+    const vt_f32x2 v = {lo, hi};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, vt_f16x2));
+#endif
+}
 template <>
-__device__ __forceinline__ u128 pack16<f16_t>(const float* f) {   // round-to-nearest-even per element
-    f16_t h[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) h[i] = from_f32<f16_t>(f[i]);
+__device__ __forceinline__ u128 pack16<f16_t>(const float* f) {
     u128 v;
-    memcpy(&v, h, 16);
+    v.x = pack_f16x2(f[0], f[1]);
+    v.y = pack_f16x2(f[2], f[3]);
+    v.z = pack_f16x2(f[4], f[5]);
+    v.w = pack_f16x2(f[6], f[7]);
     return v;
+}
+
+// two fp32 <-> one packed pair of the 16-bit type T (element 0 in the low half), round-to-nearest-even
+template <typename T>
+__device__ __forceinline__ uint32_t pack2(float lo, float hi);
+template <>
+__device__ __forceinline__ uint32_t pack2<bf16_t>(float lo, float hi) {
+    return pack_bf16x2(lo, hi);
+}
+template <>
+__device__ __forceinline__ uint32_t pack2<f16_t>(float lo, float hi) {
+    return pack_f16x2(lo, hi);
+}
+template <typename T>
+__device__ __forceinline__ void unpack2(uint32_t v, float& lo, float& hi);
+template <>
+__device__ __forceinline__ void unpack2<bf16_t>(uint32_t v, float& lo, float& hi) {
+    lo = vt_u2f(v << 16);
+    hi = vt_u2f(v & 0xffff0000u);
+}
+template <>
+__device__ __forceinline__ void unpack2<f16_t>(uint32_t v, float& lo, float& hi) {
+    f16_t h[2];
+    memcpy(h, &v, 4);
+    lo = to_f32(h[0]);
+    hi = to_f32(h[1]);
 }
 
 // ---------------------------------------------------------------------------------

@@ -60,7 +60,8 @@ class VToonifyEngine:
     """Inference engine bound to one device and one set of weights.
 
     state_dict: the reference's `g_ema` schema, fp32, on `device`.
-    dtype: torch.bfloat16 (fast) or torch.float32 (parity mode, exact-fp32 MFMA).
+    dtype: torch.bfloat16 (fast), torch.float16 (the kernels and plans of bf16 at 0.98x its frame rate, three more mantissa bits: close to the reference's
+    quality; range up to 65504) or torch.float32 (parity mode, exact-fp32 MFMA).
     x3 (fp32 only): the convolutions run as three bf16 MFMAs per fp32 product (vt_conv_desc.dtype = VT_F32X3: operands split
     into bf16 head + remainder in the fragment registers, fp32 accumulate) -- every tensor, weight and non-conv kernel stays
     fp32.  4e-5 of max|y| against the fp32 oracle (bar 1e-4) instead of 5e-6; the reference's precision at several times
@@ -74,7 +75,7 @@ class VToonifyEngine:
                  tile_hints: Optional[Dict[str, int]] = None, style_gate: bool = False, x3: bool = False,
                  fuse_rgb128: bool = True):
         assert backbone in ("dualstylegan", "toonify")
-        assert dtype in (torch.bfloat16, torch.float32)
+        assert dtype in (torch.bfloat16, torch.float16, torch.float32)
         self.backbone = backbone
         self.dual = backbone == "dualstylegan"
         self.in_size = in_size
@@ -82,8 +83,10 @@ class VToonifyEngine:
         self.dt = K.dt_code(dtype)
         self.x3 = bool(x3) and dtype == torch.float32
         self.dt_conv = K.VT_F32X3 if self.x3 else self.dt   # vt_conv_desc.dtype; everything else sees self.dt
-        self.precision = "bf16" if dtype == torch.bfloat16 else ("fp32x3" if self.x3 else "fp32_exact")
-        self.esz = 2 if dtype == torch.bfloat16 else 4
+        self.h16 = dtype in (torch.bfloat16, torch.float16)   # 16-bit activations and weights: the same plans for either type
+        self.precision = ({torch.bfloat16: "bf16", torch.float16: "fp16"}[dtype] if self.h16 else
+                          ("fp32x3" if self.x3 else "fp32_exact"))
+        self.esz = 2 if self.h16 else 4
         any_t = next(iter(state_dict.values()))
         self.device = torch.device(device) if device is not None else any_t.device
         if self.device.type == "cuda" and self.device.index is None:   # "cuda" == the current device
@@ -183,7 +186,7 @@ class VToonifyEngine:
         # fragment-stream images of the static 3x3 weights (vt_conv_weight_stream): lets vt_conv2d run the
         # few-pixel / wide-channel layers (the H/8 x W/8 trunk) on the whole-K kernel -- no split-K slabs
         self._wstream: Dict[int, torch.Tensor] = {}
-        unit = 8 * (64 if T == torch.bfloat16 else 32)
+        unit = 8 * (64 if self.h16 else 32)
         for key, wt in self.w.items():
             if wt.ndim == 3 and wt.shape[1] == 9 and wt.shape[2] % unit == 0 and wt.shape[0] % 8 == 0:
                 st = K.conv_weight_stream(wt)
@@ -191,15 +194,15 @@ class VToonifyEngine:
                     self._wstream[wt.data_ptr()] = st
 
     def _stem32(self, bi: int) -> bool:
-        """Does encoder block `bi` run on 32-channel pixel rows (bf16, a stem of <= 32 inputs -> 32 -> 32k channels)?"""
+        """Does encoder block `bi` run on 32-channel pixel rows (16-bit, a stem of <= 32 inputs -> 32 -> 32k channels)?"""
         sd = self.sd
         w0, w2 = sd[f"encoder.{bi}.0.weight"], sd[f"encoder.{bi}.2.weight"]
-        return (bi == 0 and self.dtype == torch.bfloat16 and w0.shape[1] <= 32 and w0.shape[0] == 32 and
+        return (bi == 0 and self.h16 and w0.shape[1] <= 32 and w0.shape[0] == 32 and
                 w2.shape[0] % 32 == 0 and w2.shape[0] <= 256)
 
     def _kpad(self, c: int) -> int:
-        """Channel count rounded up to the K-step of the LDS loaders (64 bf16 / 32 fp32 channels = 128 bytes)."""
-        step = 64 if self.dtype == torch.bfloat16 else 32
+        """Channel count rounded up to the K-step of the LDS loaders (64 bf16 / fp16, 32 fp32 channels = 128 bytes)."""
+        step = 64 if self.h16 else 32
         return (c + step - 1) // step * step
 
     # ------------------------------------------------------------------ plan helpers
@@ -679,7 +682,7 @@ class VToonifyEngine:
                 # (round 4 un-fused it on the 128-channel patch tiles in bf16, where the fused ToRGB had been sent back to the general
                 # epilogue after the wrong-image-row defect; with the cause found -- DESIGN.md 4.1n -- the lean / persistent kernels
                 # carry it again.  `fuse_rgb128=False` keeps round 4's two launches for A/B measurements.)
-                if fuse_rgb and not self.fuse_rgb128 and self.dt == K.VT_BF16 and tile // 100000000 == 1 and tile % 1000 == 128:
+                if fuse_rgb and not self.fuse_rgb128 and self.h16 and tile // 100000000 == 1 and tile % 1000 == 128:
                     fuse_rgb = False
                 # the LAST level's activation feeds nothing but its ToRGB: with the fused epilogue on the persistent 32 -> 32
                 # kernel it is not stored at all (67 MB per 1024^2 frame; vt_conv_desc.rgb_only)
@@ -711,7 +714,7 @@ class VToonifyEngine:
             if nb:  # zero-filled: the head of the workspace holds the split-K arrival counters
                 wss[br] = torch.zeros((nb,), dtype=torch.uint8, device=self.device)
                 plan.bufs["splitk_ws" if br == 0 else f"splitk_ws{br}"] = wss[br]
-        tname = "bf16" if self.dt == K.VT_BF16 else "f32"
+        tname = {K.VT_BF16: "bf16", K.VT_F16: "f16"}.get(self.dt, "f32")
         inserts = []
         for d, info, ops, pos in plan.convs:
             ws = wss.get(info.get("branch", 0))

@@ -176,26 +176,32 @@ class VToonify(nn.Module):
                  channel_multiplier=2, num_res_layers=6, backbone="dualstylegan",
                  compute_dtype: Optional[torch.dtype] = None, exact_fp32: Optional[bool] = None):
         """compute_dtype: the arithmetic the frame runs in.  None = the environment variable VTOONIFY_AMD_DTYPE
-        ("fp32" | "fp32_exact" | "bf16"), default **fp32** -- the reference's own precision (it is fp32 end to end,
+        ("fp32" | "fp32_exact" | "bf16" | "fp16"), default **fp32** -- the reference's own precision (it is fp32 end to end,
         model/stylegan/op/upfirdn2d_kernel.cu:311).  In fp32 every tensor, weight and non-conv kernel is fp32; the
         convolutions' products run on the bf16 matrix cores as three terms each (operands split into bf16 head + remainder
         in registers, fp32 accumulate: `VToonifyEngine(x3=True)`) -- 2-4e-5 of max|y| against the reference
         (the stated fp32 bar is 1e-4) at 1.5x the frame rate of the exact-fp32 matrix instructions, which remain one switch
         away: exact_fp32=True or VTOONIFY_AMD_DTYPE=fp32_exact (~5e-6, the bisection reference).  bf16 (PSNR >= 45 dB against
         the fp32 path) is an explicit choice: compute_dtype=torch.bfloat16 or VTOONIFY_AMD_DTYPE=bf16
-        (INTEGRATION.md 0)."""
+        (INTEGRATION.md 0).  So is fp16 (compute_dtype=torch.float16 or VTOONIFY_AMD_DTYPE=fp16 / float16): the kernels, plans
+        of bf16 at 0.98x its measured frame rate, with three more mantissa bits -- fp16 activations and weights, fp32 accumulation, statistics,
+        style path and RGB skip path.  fp16 tops out at 65504: headroom on trained weights is unmeasured, and
+        bf16 is the choice for a model that overflows."""
         super().__init__()
         env = os.environ.get("VTOONIFY_AMD_DTYPE", "fp32").lower()
-        if (compute_dtype is None or exact_fp32 is None) and env not in ("fp32", "float32", "fp32x3", "fp32_exact", "bf16", "bfloat16"):
-            raise ValueError(f"VTOONIFY_AMD_DTYPE={env!r}: expected fp32 (= fp32x3), fp32_exact or bf16")
+        if (compute_dtype is None or exact_fp32 is None) and env not in ("fp32", "float32", "fp32x3", "fp32_exact", "bf16", "bfloat16",
+                                                                         "fp16", "float16"):
+            raise ValueError(f"VTOONIFY_AMD_DTYPE={env!r}: expected fp32 (= fp32x3), fp32_exact, bf16 or fp16")
         if compute_dtype is None:
-            compute_dtype = torch.bfloat16 if env.startswith("b") else torch.float32
+            compute_dtype = (torch.bfloat16 if env.startswith("b") else torch.float16 if env in ("fp16", "float16")
+                             else torch.float32)
         if exact_fp32 is None:
             exact_fp32 = env == "fp32_exact"
         self.exact_fp32 = bool(exact_fp32)
         # the arithmetic in force, by name: "fp32x3" (fp32 tensors, conv products as three bf16 MFMAs: the default), "fp32_exact"
-        # (exact-fp32 matrix instructions, the bisection reference) or "bf16" -- what a log line / bench.py should print
-        self.precision = "bf16" if compute_dtype == torch.bfloat16 else ("fp32_exact" if exact_fp32 else "fp32x3")
+        # (exact-fp32 matrix instructions, the bisection reference), "bf16" or "fp16" -- what a log line / bench.py should print
+        self.precision = ({torch.bfloat16: "bf16", torch.float16: "fp16"}[compute_dtype]
+                          if compute_dtype in (torch.bfloat16, torch.float16) else ("fp32_exact" if exact_fp32 else "fp32x3"))
         self.backbone = backbone
         self.in_size = in_size
         self.style_channels = style_channels
