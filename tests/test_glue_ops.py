@@ -911,15 +911,17 @@ def test_grid_stride_eltwise2_gru_blend(dev, dtype):
 # entry point -> (tests that exercise it, wrapper chain or None).  With a wrapper chain ("kernels.linear", ...), the
 # tests call the first wrapper, every wrapper's source names the next one, and the last one names the entry point.
 GLUE = "test_glue_ops"
+NORM = "test_norm_native_ops"
 COVERED = {
     "vt_abi_version": (("test_abi::test_gfx950_library_exports_every_symbol",), None),
     "vt_build_target": (("test_abi::test_gfx950_library_exports_every_symbol",), None),
     "vt_last_error": (("test_ops::test_instnorm_plane_one_launch",), None),
     "vt_upfirdn2d_out_size": (("test_ops::test_upfirdn2d_golden",), ("op.upfirdn2d", "op.upfirdn2d._UpFirDn2d", "op.upfirdn2d._planes",
                                                                   "kernels.upfirdn2d_planes", "kernels.upfirdn2d_out_size")),
-    "vt_upfirdn2d": (("test_ops::test_upfirdn2d_golden",), ("op.upfirdn2d", "op.upfirdn2d._UpFirDn2d", "op.upfirdn2d._planes",
+    "vt_upfirdn2d": (("test_ops::test_upfirdn2d_golden", f"{NORM}::test_upfirdn2d_gradients"), ("op.upfirdn2d", "op.upfirdn2d._UpFirDn2d", "op.upfirdn2d._planes",
                                                          "kernels.upfirdn2d_planes")),
-    "vt_fused_bias_act": (("test_ops::test_fused_leaky_relu_golden_bit_exact",), ("op.fused_leaky_relu", "op.fused_act._FusedLeakyReLU",
+    "vt_fused_bias_act": (("test_ops::test_fused_leaky_relu_golden_bit_exact", f"{NORM}::test_fused_leaky_relu_gradients",
+                           f"{NORM}::test_fused_bias_act_modes_and_forms", f"{NORM}::test_grid_stride_fused_bias_act_flat"), ("op.fused_leaky_relu", "op.fused_act._FusedLeakyReLU",
                                                                                    "kernels.fused_bias_act")),
     "vt_conv2d": (("test_ops::test_conv_fused_torgb",), ("kernels.conv2d",)),
     "vt_conv2d_tile": (("test_ops::test_conv_thin_kernel",), None),
@@ -939,14 +941,21 @@ COVERED = {
     "vt_modulate_weight_batch_gated": ((f"{GLUE}::test_modulate_weight_batch",), None),
     "vt_pixel_norm_gated": ((f"{GLUE}::test_pixel_norm",), None),
     "vt_instnorm_ws_bytes": ((f"{GLUE}::test_channel_mean",), ("kernels.instnorm_ws_bytes",)),
-    "vt_instnorm_stats": (("test_ops::test_instnorm_adain_fusion_pack",), ("kernels.instnorm_stats",)),
-    "vt_instnorm_apply": (("test_ops::test_conv_emits_instnorm_records",), None),
-    "vt_instnorm_apply_stats": (("test_ops::test_conv_emits_instnorm_records",), None),
-    "vt_instnorm_plane": (("test_ops::test_instnorm_plane_one_launch",), None),
-    "vt_affine_apply": (("test_ops::test_instnorm_adain_fusion_pack",), ("kernels.affine_apply",)),
-    "vt_fusion_pack": (("test_ops::test_instnorm_adain_fusion_pack",), ("kernels.fusion_pack",)),
-    "vt_frame_pack": (("test_video::test_frame_pack_unpack_vs_oracle",), ("video.frame_pack",)),
-    "vt_frame_unpack": (("test_video::test_frame_pack_unpack_vs_oracle",), ("video.frame_unpack",)),
+    "vt_instnorm_stats": (("test_ops::test_instnorm_adain_fusion_pack", f"{NORM}::test_instnorm_chunked_shapes",
+                           f"{NORM}::test_instnorm_chunked_numerics", f"{NORM}::test_instnorm_constant_plane"), ("kernels.instnorm_stats",)),
+    "vt_instnorm_apply": (("test_ops::test_conv_emits_instnorm_records", f"{NORM}::test_instnorm_chunked_shapes",
+                           f"{NORM}::test_instnorm_chunked_numerics", f"{NORM}::test_instnorm_apply_plane_limit"), None),
+    "vt_instnorm_apply_stats": (("test_ops::test_conv_emits_instnorm_records", f"{NORM}::test_instnorm_chunked_shapes",
+                                 f"{NORM}::test_instnorm_apply_plane_limit"), None),
+    "vt_instnorm_plane": (("test_ops::test_instnorm_plane_one_launch", f"{NORM}::test_instnorm_plane",
+                           f"{NORM}::test_instnorm_constant_plane"), None),
+    "vt_affine_apply": (("test_ops::test_instnorm_adain_fusion_pack", f"{NORM}::test_instnorm_chunked_shapes",
+                         f"{NORM}::test_grid_stride_affine_apply_fusion_pack"), ("kernels.affine_apply",)),
+    "vt_fusion_pack": (("test_ops::test_instnorm_adain_fusion_pack", f"{NORM}::test_fusion_pack",
+                        f"{NORM}::test_grid_stride_affine_apply_fusion_pack"), ("kernels.fusion_pack",)),
+    "vt_frame_pack": (("test_video::test_frame_pack_unpack_vs_oracle", f"{NORM}::test_frame_pack", f"{NORM}::test_grid_stride_frame_io"), ("video.frame_pack",)),
+    "vt_frame_unpack": (("test_video::test_frame_pack_unpack_vs_oracle", f"{NORM}::test_frame_unpack",
+                         f"{NORM}::test_grid_stride_frame_io"), ("video.frame_unpack",)),
     "vt_channel_mean": ((f"{GLUE}::test_channel_mean",), None),
     "vt_se_apply": ((f"{GLUE}::test_se_apply",), None),
     "vt_upsample_bilinear_add": ((f"{GLUE}::test_upsample_bilinear_add", f"{GLUE}::test_grid_stride_upsample_bilinear_add"),
@@ -960,8 +969,10 @@ COVERED = {
     "vt_parsing_fuse": ((f"{GLUE}::test_parsing_fuse",), None),
     "vt_eltwise2": ((f"{GLUE}::test_grid_stride_eltwise2_gru_blend", "test_raft_net::test_glue_kernels"), None),
     "vt_gru_blend": ((f"{GLUE}::test_grid_stride_eltwise2_gru_blend", "test_raft_net::test_glue_kernels"), None),
-    "vt_coords_from_flow": (("test_raft_net::test_glue_kernels",), None),
-    "vt_convex_upsample": (("test_raft_net::test_glue_kernels",), None),
+    "vt_coords_from_flow": (("test_raft_net::test_glue_kernels", f"{NORM}::test_raft_glue_kernels", f"{NORM}::test_grid_stride_raft_glue"),
+                            None),
+    "vt_convex_upsample": (("test_raft_net::test_glue_kernels", f"{NORM}::test_raft_glue_kernels", f"{NORM}::test_grid_stride_raft_glue"),
+                           None),
     "vt_nchw_to_nhwc": (("test_ops::test_layout_change_at_the_model_boundary",), ("kernels.nchw_to_nhwc",)),
     "vt_nhwc_to_nchw": (("test_ops::test_layout_change_back_to_planes",), None),
     "vt_mfma_selftest": (("test_ops::test_mfma_lane_maps",), ("kernels.mfma_selftest",)),

@@ -39,6 +39,17 @@ __device__ __forceinline__ float act_apply(float x, float ref, int use_ref, int 
     return y;
 }
 
+// The fp32 result, rounded ONCE to the tensor's type.  For fp16 the compiler otherwise fuses the multiply by `scale` and the
+// conversion into v_fma_mixlo_f16 with a +0 addend: the exact product rounded straight to fp16 (not the reference's fp32
+// result), and -0 turned into +0.  The empty asm keeps the product in a register of its own; it emits no instruction.
+template <typename T>
+__device__ __forceinline__ T store_cvt(float p) {
+#ifndef VT_EMU
+    asm volatile("" : "+v"(p));
+#endif
+    return from_f32<T>(p);
+}
+
 // One workgroup = 256 threads = a contiguous chunk of one plane.
 template <typename T, int VEC>
 __global__ void __launch_bounds__(256)
@@ -66,17 +77,19 @@ fba_plane_kernel(T* __restrict__ out, const T* __restrict__ x, const T* __restri
             T* eo = reinterpret_cast<T*>(&vo);
 #pragma unroll
             for (int j = 0; j < VEC; ++j) {
-                float v = to_f32(ex[j]) + b;
+                float v = to_f32(ex[j]);
+                if (bias) v += b;   // no add without a bias: x = -0.0 keeps its sign, as in the reference kernel and the flat form
                 v = act_apply(v, to_f32(er[j]), refer != nullptr, mode, alpha);
-                eo[j] = from_f32<T>(v * scale);
+                eo[j] = store_cvt<T>(v * scale);
             }
             st128(out + base + off, vo);
         } else {
             for (int j = 0; j < VEC && off + j < step_b; ++j) {
-                float v = to_f32(x[base + off + j]) + b;
+                float v = to_f32(x[base + off + j]);
+                if (bias) v += b;
                 float r = refer ? to_f32(refer[base + off + j]) : 0.0f;
                 v = act_apply(v, r, refer != nullptr, mode, alpha);
-                out[base + off + j] = from_f32<T>(v * scale);
+                out[base + off + j] = store_cvt<T>(v * scale);
             }
         }
     }
@@ -93,7 +106,7 @@ fba_flat_kernel(T* __restrict__ out, const T* __restrict__ x, const T* __restric
         if (bias) v += to_f32(bias[(i / step_b) % size_b]);
         float r = refer ? to_f32(refer[i]) : 0.0f;
         v = act_apply(v, r, refer != nullptr, mode, alpha);
-        out[i] = from_f32<T>(v * scale);
+        out[i] = store_cvt<T>(v * scale);
     }
 }
 
