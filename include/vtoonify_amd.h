@@ -483,4 +483,8 @@ int vt_mfma_selftest(float* c, const void* a, const void* b, int dtype, vt_strea
 #ifdef __cplusplus
 }
 #endif
+
+/* The entry points of the streaming flicker-reduction pre-pass (same library, same conventions) are declared in their own
+ * header; DESIGN.md 4.6 says why. */
+#include "vtoonify_amd_prepass.h"
 #endif /* VTOONIFY_AMD_H */

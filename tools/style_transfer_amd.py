@@ -6,6 +6,9 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         tools/style_transfer_amd.py --content clip.npy --video --parsing_map_path maps.npy ...
 
+`--smooth_window N` puts the flicker-reduction pre-pass (smooth_parsing_map.py; tools/smooth_parsing_map_amd.py) in front of the
+loop: one command for the reference's two, no .npy in between; each rank reads N frames of context around its shard.
+
 The 16 options of the reference (style_transfer.py:17-46) keep their names, types, defaults and meaning; the loop is the
 reference's (:99-183) with its host work moved to the GPU (vtoonify_amd/video.py) and its frames cut into one contiguous
 shard per rank (vtoonify_amd/frames.py: rank 0 reads the checkpoint and the style code, ONE bucketed RCCL broadcast
@@ -43,8 +46,8 @@ from vtoonify_amd import _lib, frames, synth  # noqa: E402
 from vtoonify_amd.video import VideoToonifier, frame_pack  # noqa: E402
 from vtoonify_amd.vtoonify import VToonify  # noqa: E402
 
-VIDEO_EXT = (".mp4", ".avi", ".mov", ".mkv", ".webm")
-IMAGE_EXT = (".jpg", ".jpeg", ".png", ".bmp")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from frame_sources import IMAGE_EXT, VIDEO_EXT, Cv2Source, DirSource, NpySource, open_source  # noqa: E402,F401
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -76,6 +79,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help=".npy (1,18,512): the style encoder's output for this video (skips the pSp pass and the face alignment)")
     p.add_argument("--max_frames", type=int, default=None, help="stop after this many frames")
     p.add_argument("--seed", type=int, default=0, help="seed of `synthetic` weights")
+    p.add_argument("--smooth_window", type=int, default=0,
+                   help="N > 0 with --video: temporally smooth the parsing maps over 2N+1 frames first (smooth_parsing_map.py's "
+                        "--window_size; the two-step workflow in one command); 0 = off")
+    p.add_argument("--raft_path", type=str, default="./checkpoint/raft-things.pth",
+                   help="path of the RAFT model (smooth_parsing_map.py's option), used with --smooth_window")
+    p.add_argument("--smooth_iters", type=int, default=20, help="RAFT iterations of --smooth_window (20 = smooth_parsing_map.py:154)")
     return p
 
 
@@ -87,90 +96,6 @@ def parse(argv=None):
 
 
 # ----------------------------------------------------------------------------------------- frame sources / sinks
-class NpySource:
-    """(N,H,W,3) uint8 .npy, memory-mapped; random access, so every rank reads only its shard."""
-    kind = "npy"
-
-    def __init__(self, path, bgr):
-        self.a = np.load(path, mmap_mode="r")
-        if self.a.ndim == 3:
-            self.a = self.a[None]
-        if self.a.ndim != 4 or self.a.shape[3] != 3 or self.a.dtype != np.uint8:
-            raise ValueError(f"{path}: expected (N,H,W,3) uint8 frames")
-        self.bgr, self.fps = bgr, 25.0
-
-    def __len__(self):
-        return self.a.shape[0]
-
-    def frames(self, start, stop):
-        for i in range(start, stop):
-            yield np.ascontiguousarray(self.a[i])
-
-
-class DirSource:
-    kind = "dir"
-
-    def __init__(self, path, bgr):
-        self.files = sorted(os.path.join(path, f) for f in os.listdir(path) if f.endswith(".npy"))
-        if not self.files:
-            raise ValueError(f"{path}: no *.npy frames")
-        self.bgr, self.fps = bgr, 25.0
-
-    def __len__(self):
-        return len(self.files)
-
-    def frames(self, start, stop):
-        for f in self.files[start:stop]:
-            yield np.ascontiguousarray(np.load(f))
-
-
-class Cv2Source:
-    """cv2.VideoCapture / cv2.imread: BGR frames, as the reference reads them (style_transfer.py:103-112,188)."""
-
-    def __init__(self, path, video):
-        import cv2
-        self.cv2, self.path, self.video, self.bgr = cv2, path, video, True
-        self.kind = "video" if video else "image"
-        if video:
-            cap = cv2.VideoCapture(path)
-            self.n, self.fps = int(cap.get(7)), cap.get(5)
-            cap.release()
-        else:
-            self.n, self.fps = 1, 25.0
-
-    def __len__(self):
-        return self.n
-
-    def frames(self, start, stop):
-        if not self.video:
-            yield self.cv2.imread(self.path)
-            return
-        cap = self.cv2.VideoCapture(self.path)
-        cap.set(self.cv2.CAP_PROP_POS_FRAMES, start)
-        for _ in range(start, stop):
-            ok, fr = cap.read()
-            if not ok:
-                break
-            yield fr
-        cap.release()
-
-
-def open_source(path, video, frame_order):
-    ext = os.path.splitext(path)[1].lower()
-    if os.path.isdir(path):
-        return DirSource(path, frame_order == "bgr")
-    if ext == ".npy":
-        return NpySource(path, frame_order == "bgr")
-    if ext in VIDEO_EXT + IMAGE_EXT:
-        try:
-            import cv2  # noqa: F401
-        except ImportError:
-            raise SystemExit(f"{path}: reading {ext} needs cv2 (not importable here); pass frames as .npy "
-                             "((N,H,W,3) uint8) or a directory of .npy frames") from None
-        return Cv2Source(path, video and ext in VIDEO_EXT)
-    raise SystemExit(f"{path}: unknown content type")
-
-
 class NpySink:
     """One (N,4H,4W,3) uint8 .npy; rank 0 creates it, every rank writes its own rows: the file is in frame order without
     a gather (one node, one file system)."""
@@ -382,8 +307,18 @@ def main(argv=None, device=None, backend=None) -> dict:
 
     # ---- parsing maps: given (--parsing_map_path, style_transfer.py:168-169) or computed on the GPU (:170-172) ----
     maps = np.load(opt.parsing_map_path, mmap_mode="r") if (opt.video and opt.parsing_map_path) else None
+    smoother = None
+    if opt.smooth_window > 0:
+        if not opt.video or maps is not None or not on_engine:
+            raise SystemExit("--smooth_window needs --video on the GPU and excludes --parsing_map_path (it computes those maps)")
+        import smooth_parsing_map_amd as spm
+        from vtoonify_amd.smooth import ParsingSmoother
+        # the pre-pass in the arithmetic of its own command line's default (fp32), whatever the frame's precision: one
+        # command gives what smooth_parsing_map_amd.py followed by --parsing_map_path gives
+        raft, par_s = spm.load_models(opt, device, torch.float32)
+        smoother = ParsingSmoother(raft, par_s, opt.smooth_window, iters=opt.smooth_iters, bgr=src.bgr)
     # (the parsing network has no fp16 form: it runs in bf16 beside an fp16 frame)
-    par = None if maps is not None else parsing_engine(opt, device, torch.bfloat16 if cdt == torch.float16 else cdt)
+    par = None if (maps is not None or smoother is not None) else parsing_engine(opt, device, torch.bfloat16 if cdt == torch.float16 else cdt)
 
     base = os.path.basename(opt.content.rstrip("/")).split(".")[0]
     stem = os.path.join(opt.output_path, f"{base}_vtoonify_{opt.backbone[0]}")
@@ -409,6 +344,24 @@ def main(argv=None, device=None, backend=None) -> dict:
             fr = (fr if crop is None else crop(fr))[:H, :W]
             yield fr, (None if maps is None else np.asarray(maps[a + j], dtype=np.float32)[:, :H, :W])
 
+    def smoothed_source():
+        """The shard's frames with w frames of context on either side (the neighbour shard's real frames; only the clip's own
+        ends replicate), smoothed maps alongside: what --parsing_map_path would have read for these frames."""
+        import collections
+        w, held = opt.smooth_window, collections.deque()
+        lo, hi = max(0, a - w), min(n, b + w)
+
+        def feed():
+            for j, fr in enumerate(src.frames(lo, hi)):
+                fr = fr if crop is None else crop(fr)
+                if a <= lo + j < b:
+                    held.append(fr)
+                yield np.ascontiguousarray(fr)
+        for p in smoother.smooth_shard(feed(), n, a, b):
+            yield held.popleft()[:H, :W], np.ascontiguousarray(p[0].cpu().numpy()[:, :H, :W])
+
+    if smoother is not None:
+        shard_source = smoothed_source
     t0 = time.time()
     local = [] if gather else None
     emit = (lambda i, fr: local.append(fr.copy())) if gather else sink

@@ -146,6 +146,12 @@ _SIGS = {
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
+# include/vtoonify_amd_prepass.h: the streaming flicker-reduction pre-pass, additive to ABI version 5
+_PREPASS_SIGS = {
+    "vt_frame_ingest2x": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
+}
+PREPASS_SYMBOLS = tuple(_PREPASS_SIGS)
+
 _lib = None
 _lib_path = None
 
@@ -157,7 +163,7 @@ def _bind(path: str):
     # "no ROCm-capable device is detected" at the first launch.)
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    for name, (res, args) in _SIGS.items():
+    for name, (res, args) in {**_SIGS, **_PREPASS_SIGS}.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args

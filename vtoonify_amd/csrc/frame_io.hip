@@ -11,11 +11,22 @@
 //                                                                      tensor2cv2 util.py:190-192)
 //                    with the RGB->BGR swap of tensor2cv2 folded in.
 //
-// Both are pure streaming kernels: 4 pixels per lane (12 payload bytes <-> three 16-byte plane
+//   vt_frame_ingest2x  uint8 HWC frames -> the three tensors of the flicker-reduction pre-pass at twice the frame size, in
+//                    one read of the frame (smooth_parsing_map.py:86-89,128,136,154):
+//                      Is      = F.upsample(Normalize(ToTensor(frame)), scale_factor=2, mode='bilinear')
+//                      raft    = (Is + 1) * 255.0 / 2          RAFT's network input in [0, 255]
+//                      bisenet = 2 * Is                        BiSeNet's network input
+//                    all planar fp32 (n,3,2h,2w), the layout RaftEngine.encode / BiSeNetEngine.forward take.
+//
+// The first two are pure streaming kernels: 4 pixels per lane (12 payload bytes <-> three 16-byte plane
 // vectors), every plane access a coalesced 16-byte vector.  The fp32 arithmetic is the reference's op
 // sequence (div, sub, div / add, mul, truncate), unfused, so results are BIT-exact against the
 // numpy / torch formulas (tests/test_video.py).
-// Algorithmic bytes: pack  n*h*w*(3 + 4*(3+pc) + 4*pc);  unpack  n*H*W*(12 + 3).
+// vt_frame_ingest2x: one lane per output pixel; the four source pixels are 12 cached bytes, the nine stores of a wave are
+// coalesced 256-byte rows.  Source index and lerp follow aten (area_pixel_compute_source_index with scale 0.5,
+// align_corners=False; h0 * (w0 * a + w1 * b) + h1 * (w0 * c + w1 * d)), the two affine images are the reference's op
+// sequences, unfused.
+// Algorithmic bytes: pack  n*h*w*(3 + 4*(3+pc) + 4*pc);  unpack  n*H*W*(12 + 3);  ingest2x  n*h*w*(3 + 4*3*4*3).
 #include "vt_common.hpp"
 
 namespace {
@@ -118,6 +129,50 @@ frame_unpack_kernel(unsigned char* __restrict__ frames, const float* __restrict_
     }
 }
 
+// aten area_pixel_compute_source_index(scale = 0.5, align_corners = false) + guard_index_and_lambda
+__device__ __forceinline__ void up2_tap(int dst, int in_size, int& i0, int& i1, float& l0, float& l1) {
+    float src = 0.5f * ((float)dst + 0.5f) - 0.5f;
+    if (src < 0.0f) src = 0.0f;
+    i0 = (int)src;
+    if (i0 > in_size - 1) i0 = in_size - 1;
+    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
+    l1 = src - (float)i0;
+    l0 = 1.0f - l1;
+}
+
+// one thread = one output pixel (Y, X) of one image, its three channels and three destinations
+__global__ void __launch_bounds__(256)
+frame_ingest2x_kernel(float* __restrict__ is, float* __restrict__ raft, float* __restrict__ bise,
+                      const unsigned char* __restrict__ frames, int n, int h, int w, int swap_rb) {
+    const int oh = 2 * h, ow = 2 * w;
+    const int64_t ohw = (int64_t)oh * ow;
+    const int64_t total = (int64_t)n * ohw;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int img = (int)(i / ohw);
+        const int64_t rem = i - (int64_t)img * ohw;
+        const int Y = (int)(rem / ow), X = (int)(rem - (int64_t)Y * ow);
+        int y0, y1, x0, x1;
+        float ly0, ly1, lx0, lx1;
+        up2_tap(Y, h, y0, y1, ly0, ly1);
+        up2_tap(X, w, x0, x1, lx0, lx1);
+        const unsigned char* f = frames + (int64_t)img * h * w * 3;
+        const unsigned char* p00 = f + ((int64_t)y0 * w + x0) * 3;
+        const unsigned char* p01 = f + ((int64_t)y0 * w + x1) * 3;
+        const unsigned char* p10 = f + ((int64_t)y1 * w + x0) * 3;
+        const unsigned char* p11 = f + ((int64_t)y1 * w + x1) * 3;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const int sc = swap_rb ? 2 - ch : ch;
+            const float v = ly0 * (lx0 * norm_u8(p00[sc]) + lx1 * norm_u8(p01[sc])) +
+                            ly1 * (lx0 * norm_u8(p10[sc]) + lx1 * norm_u8(p11[sc]));
+            const int64_t o = ((int64_t)img * 3 + ch) * ohw + rem;
+            is[o] = v;
+            if (raft) raft[o] = (v + 1.0f) * 255.0f / 2.0f;
+            if (bise) bise[o] = 2.0f * v;
+        }
+    }
+}
+
 inline unsigned grid_for(int64_t total) {
     int64_t b = (total + 255) / 256;
     if (b > 65536) b = 65536;
@@ -161,4 +216,14 @@ extern "C" int vt_frame_unpack(uint8_t* frames, const float* image, int swap_rb,
         VT_LAUNCH(k, dim3(grid_for((int64_t)n * hw)), dim3(256), stream, (unsigned char*)frames, image, n, hw, swap_rb);
     }
     return vt_check_launch("vt_frame_unpack");
+}
+
+extern "C" int vt_frame_ingest2x(float* is, float* raft_in, float* bisenet_in, const uint8_t* frames, int swap_rb, int n,
+                                 int h, int w, vt_stream stream) {
+    VT_REQUIRE(is && frames, "vt_frame_ingest2x: null tensor");
+    VT_REQUIRE(n > 0 && h > 0 && w > 0 && (int64_t)h * w < ((int64_t)1 << 28), "vt_frame_ingest2x: bad sizes");
+    auto k = frame_ingest2x_kernel;
+    VT_LAUNCH(k, dim3(grid_for((int64_t)n * h * w * 4)), dim3(256), stream, is, raft_in, bisenet_in,
+              (const unsigned char*)frames, n, h, w, swap_rb);
+    return vt_check_launch("vt_frame_ingest2x");
 }

@@ -288,6 +288,21 @@ def nhwc_to_nchw(x_ptr, ld_in, n, c, h, w, in_dtype, out_dtype, device, stream_o
     return out
 
 
+def frame_ingest2x(frames_u8: torch.Tensor, bgr: bool = True, raft: bool = True, bisenet: bool = True):
+    """(N,H,W,3) uint8 -> (Is, raft_in, bisenet_in), each (N,3,2H,2W) fp32 (vt_frame_ingest2x): Is = the 2x bilinear
+    up-sampling of Normalize(ToTensor(frame)) (smooth_parsing_map.py:86-89,128), raft_in = (Is + 1) * 255 / 2 (:154),
+    bisenet_in = 2 * Is (:136); an output that is switched off is None."""
+    if frames_u8.dtype != torch.uint8 or frames_u8.ndim != 4 or frames_u8.shape[-1] != 3:
+        raise _lib.VtError("frame_ingest2x: frames must be (N,H,W,3) uint8")
+    _dev_ok(frames_u8)
+    n, h, w, _ = frames_u8.shape
+    new = lambda: torch.empty((n, 3, 2 * h, 2 * w), dtype=torch.float32, device=frames_u8.device)
+    Is, r, b = new(), new() if raft else None, new() if bisenet else None
+    _lib.check(_lib.lib().vt_frame_ingest2x(_p(Is), _p(r), _p(b), _p(frames_u8), int(bool(bgr)), n, h, w,
+                                            _stream(frames_u8)), "vt_frame_ingest2x")
+    return Is, r, b
+
+
 def mfma_selftest(a: torch.Tensor, b: torch.Tensor):
     _dev_ok(a, b)
     c = torch.empty((16, 16), dtype=torch.float32, device=a.device)

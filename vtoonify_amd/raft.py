@@ -2,6 +2,9 @@
 (smooth_parsing_map.py:95-102,154: `RAFT(args)`, `raft_model(image1, image2, iters=20, test_mode=True)`;
 model/raft/core/raft.py, extractor.py, update.py, corr.py).
 
+`RaftEngine.encode(image)` / `RaftEngine.refine(feat_center, feats_neighbours, iters)` are the two halves of forward -- what
+depends on one frame, and what depends on a pair -- for callers that meet the same frame in many pairs (smooth.ParsingSmoother).
+
 `RAFT(args)` keeps the reference's constructor, state_dict schema (179 entries: fnet / cnet / update_block, BatchNorm
 buffers included, the shared `norm3` / `downsample.1` entries too) and `forward(image1, image2, iters=12,
 flow_init=None, upsample=True, test_mode=False)`; `RaftEngine` runs it:
@@ -163,6 +166,30 @@ class RAFT(nn.Module):
 # ---------------------------------------------------------------------------------------------------------
 # engine
 # ---------------------------------------------------------------------------------------------------------
+class RaftFeatures:
+    """Per-frame output of RaftEngine.encode for a batch of N frames: fmap (N,h,w,256) fp32, pyramid = [fmap and its three
+    2x2 averages], ctx (N,h,w,HX) GRU input rows with net | inp filled in.  feats[i] is frame i alone (views)."""
+
+    def __init__(self, fmap, pyramid, ctx):
+        self.fmap, self.pyramid, self.ctx = fmap, pyramid, ctx
+
+    def __len__(self):
+        return self.fmap.shape[0]
+
+    def __getitem__(self, i):
+        i = int(i)
+        return RaftFeatures(self.fmap[i:i + 1], [p[i:i + 1] for p in self.pyramid], self.ctx[i:i + 1])
+
+    @staticmethod
+    def cat(feats):
+        return RaftFeatures(torch.cat([f.fmap for f in feats], 0),
+                            [torch.cat([f.pyramid[l] for f in feats], 0) for l in range(len(feats[0].pyramid))],
+                            torch.cat([f.ctx for f in feats], 0))
+
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in [self.ctx] + list(self.pyramid))
+
+
 class RaftEngine:
     def __init__(self, sd: Dict[str, torch.Tensor], dtype=torch.float32, device="cuda"):
         self.device = torch.device(device)
@@ -349,29 +376,51 @@ class RaftEngine:
         image2 = image2.to(self.device, torch.float32).contiguous()
         self._anchor = image1
         K._dev_ok(image1, image2)
-        # 2 * (x / 255) - 1 (raft.py:89-90) on the NHWC copy; the 5 padding channels stay zero
-        sc = torch.zeros((2 * N, 8), device=self.device)
-        sh = torch.zeros((2 * N, 8), device=self.device)
-        sc[:, :3], sh[:, :3] = 2.0 / 255.0, -1.0
-        both = K.nchw_to_nhwc(torch.cat([image1, image2], 0), self.dtype)     # (2N,H,W,8): fnet([image1, image2])
-        xn = torch.empty_like(both)
-        K.affine_apply(xn, 8, both, 8, sc, sh, 2 * N, H * W, 8, self.dt, stream_of=both)
-
+        xn = self._normalise(torch.cat([image1, image2], 0))                  # (2N,H,W,8): fnet([image1, image2])
         # feature network (instance norm) on both frames, context network (folded batch norm) on the first
-        f, h, w = self._encoder("fnet.", xn, 2 * N, H, W, True)
-        fmap = self._buf((2 * N, h, w, 256), torch.float32)
-        self._conv("fnet.conv2", f, 128, 128, 2 * N, h, w, 256, 1, 1, self._fmap_out(fmap), 256)
-        fmap = self._fmap_done(fmap)
+        fmap, h, w = self._fnet(xn, 2 * N, H, W)
         fmap1, fmap2 = fmap[:N].contiguous(), fmap[N:].contiguous()
+        hx = self._cnet(xn[:N].contiguous(), N, H, W)
+        return self._refine(fmap1, self._pyramid(fmap2), hx, iters, flow_init, all_predictions)
+
+    def _normalise(self, image):
+        """2 * (x / 255) - 1 (raft.py:89-90) on the NHWC copy; the 5 padding channels stay zero."""
+        n, _, H, W = image.shape
+        sc = torch.zeros((n, 8), device=self.device)
+        sh = torch.zeros((n, 8), device=self.device)
+        sc[:, :3], sh[:, :3] = 2.0 / 255.0, -1.0
+        x8 = K.nchw_to_nhwc(image, self.dtype)
+        xn = torch.empty_like(x8)
+        K.affine_apply(xn, 8, x8, 8, sc, sh, n, H * W, 8, self.dt, stream_of=x8)
+        return xn
+
+    def _fnet(self, xn, n, H, W):
+        f, h, w = self._encoder("fnet.", xn, n, H, W, True)
+        fmap = self._buf((n, h, w, 256), torch.float32)
+        self._conv("fnet.conv2", f, 128, 128, n, h, w, 256, 1, 1, self._fmap_out(fmap), 256)
+        return self._fmap_done(fmap), h, w
+
+    @staticmethod
+    def _pyramid(fmap2):
         pyramid = [fmap2]
         for _ in range(3):     # corr_levels = 4
             pyramid.append(raft_corr.avg_pool2x2_nhwc(pyramid[-1]))
-        c, h, w = self._encoder("cnet.", xn[:N].contiguous(), N, H, W, False)
-        hx = self._buf((N, h, w, HX), zero=True)
-        base = hx.data_ptr()
-        self._conv("cnet.net", c, 128, 128, N, h, w, 128, 1, 1, base, HX, act=ACT_TANH)                       # net = tanh(.)
-        self._conv("cnet.inp", c, 128, 128, N, h, w, 128, 1, 1, base + 128 * self.esz, HX, act=ACT_LRELU, slope=0.0)
+        return pyramid
 
+    def _cnet(self, xn, n, H, W):
+        """The GRU input rows (n,h,w,HX) with [net = tanh(.) | inp = relu(.)] of the context network filled in."""
+        c, h, w = self._encoder("cnet.", xn, n, H, W, False)
+        hx = self._buf((n, h, w, HX), zero=True)
+        base = hx.data_ptr()
+        self._conv("cnet.net", c, 128, 128, n, h, w, 128, 1, 1, base, HX, act=ACT_TANH)                       # net = tanh(.)
+        self._conv("cnet.inp", c, 128, 128, n, h, w, 128, 1, 1, base + 128 * self.esz, HX, act=ACT_LRELU, slope=0.0)
+        return hx
+
+    def _refine(self, fmap1, pyramid, hx, iters, flow_init, all_predictions):
+        """The update iterations (raft.py:115-144) from the features of the pairs: fmap1 (N,h,w,256) fp32, the 2x2-average
+        pyramid of fmap2, hx (N,h,w,HX) as _cnet leaves it (updated in place)."""
+        N, h, w, _ = fmap1.shape
+        base = hx.data_ptr()
         taps = {"cnet": hx[..., :256].clone()} if self.keep_taps else {}
         flow = torch.zeros((N, 2, h, w), device=self.device)              # coords1 - coords0
         if flow_init is not None:
@@ -431,6 +480,50 @@ class RaftEngine:
         taps["fmap1"] = fmap1
         self.taps = taps
         return flow.clone(), ups
+
+    # ------------------------------------------------------------------ the two halves of forward
+    @torch.no_grad()
+    def encode(self, image: torch.Tensor) -> "RaftFeatures":
+        """Everything of forward that depends on ONE frame: image (N,3,H,W) in [0,255], H and W multiples of 8 ->
+        the fnet map, its 2x2-average pyramid (what the correlation lookup reads when the frame is a pair's second
+        image) and cnet's net / inp (what the GRU starts from when it is the first).  InstanceNorm of fnet is per image,
+        so a frame's features do not depend on the batch it was encoded in -- to the bit when the conv plans do not look
+        at the batch size either (VT_BATCH_EXACT=1)."""
+        self.lib = _lib.lib()
+        if image.ndim != 4 or image.shape[1] != 3:
+            raise _lib.VtError("RAFT.encode: image must be (N,3,H,W)")
+        N, _, H, W = image.shape
+        if H % 8 or W % 8:
+            raise _lib.VtError("RAFT: H and W must be multiples of 8 (pad with InputPadder first)")
+        image = image.to(self.device, torch.float32).contiguous()
+        self._anchor = image
+        K._dev_ok(image)
+        xn = self._normalise(image)
+        fmap, h, w = self._fnet(xn, N, H, W)
+        return RaftFeatures(fmap, self._pyramid(fmap), self._cnet(xn, N, H, W))
+
+    @torch.no_grad()
+    def refine(self, feat_center: "RaftFeatures", feats_neighbours, iters: int = 20) -> torch.Tensor:
+        """flow_up (N,2,H,W) of the N pairs (centre, neighbour_j) from cached features: the correlation lookup and `iters`
+        update iterations of forward(test_mode).  feat_center holds one frame (shared by every pair) or N;
+        feats_neighbours is a RaftFeatures of N frames or a list of them."""
+        self.lib = _lib.lib()
+        if isinstance(feats_neighbours, RaftFeatures):
+            pyramid = [p.contiguous() for p in feats_neighbours.pyramid]
+        else:      # per-frame features: only what the lookup reads is gathered
+            fs = list(feats_neighbours)
+            pyramid = [torch.cat([f.pyramid[l] for f in fs], 0) for l in range(len(fs[0].pyramid))]
+        N = pyramid[0].shape[0]
+        if feat_center.fmap.shape[0] == 1 and N > 1:
+            fmap1, hx = feat_center.fmap.repeat(N, 1, 1, 1), feat_center.ctx.repeat(N, 1, 1, 1)
+        elif feat_center.fmap.shape[0] == N:
+            fmap1, hx = feat_center.fmap.contiguous(), feat_center.ctx.clone()
+        else:
+            raise _lib.VtError("RAFT.refine: the centre holds one frame or as many as there are neighbours")
+        if fmap1.shape[1:] != pyramid[0].shape[1:]:
+            raise _lib.VtError("RAFT.refine: centre and neighbours differ in size")
+        self._anchor = fmap1
+        return self._refine(fmap1, pyramid, hx, iters, None, False)[1][-1]
 
     # fmap is consumed by the fp32 correlation lookup: in fp32 mode the conv writes it directly
     def _fmap_out(self, fmap):
