@@ -487,4 +487,6 @@ int vt_mfma_selftest(float* c, const void* a, const void* b, int dtype, vt_strea
 /* The entry points of the streaming flicker-reduction pre-pass (same library, same conventions) are declared in their own
  * header; DESIGN.md 4.6 says why. */
 #include "vtoonify_amd_prepass.h"
+/* ... and those for source-size frames (--scale_image on the GPU). */
+#include "vtoonify_amd_frames.h"
 #endif /* VTOONIFY_AMD_H */

@@ -20,9 +20,11 @@ serving image need not carry:
             *.npy                          -> (N,H,W,3) uint8 array (memory-mapped), channel order --frame_order
             a directory                    -> sorted *.npy frames (H,W,3) uint8
   output    the same kind as the content: `<basename>_vtoonify_<d|t>.mp4|.npy|/` under --output_path
-`--scale_image` (FaceCrop below: the reference's resize + crop from the first frame's eye distance) and the aligned style
-crop need the face landmarks of dlib and cv2's filter / resize (util.py:163-188, model/encoder/align_all_parallel.py);
-without them pass pre-cropped frames, and either `--intrinsic_code` (the pSp encoder's (1,18,512) output, .npy) or accept
+`--scale_image` (the reference's resize + crop from the first frame's eye distance, util.py:163-188) runs on the GPU by default
+(`--scale_on gpu`: vtoonify_amd/scale.py, one kernel per batch over source-size frames) and needs only the first frame's 68
+face landmarks: `--landmarks lm.npy`, or dlib when it is importable.  `--scale_on host` is the reference's own per-frame cv2
+calls (FaceCrop below; needs cv2).  The aligned style crop needs dlib (model/encoder/align_all_parallel.py); without it pass
+either `--intrinsic_code` (the pSp encoder's (1,18,512) output, .npy) or accept
 the un-aligned first frame as the style encoder's input (a warning is printed).
 `--ckpt synthetic` / `--style_encoder_path synthetic` / `--faceparsing_path synthetic` build seeded random weights of the
 reference's schema (there are no checkpoints on the benchmark boxes); everything else is the reference's behaviour.
@@ -79,6 +81,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help=".npy (1,18,512): the style encoder's output for this video (skips the pSp pass and the face alignment)")
     p.add_argument("--max_frames", type=int, default=None, help="stop after this many frames")
     p.add_argument("--seed", type=int, default=0, help="seed of `synthetic` weights")
+    p.add_argument("--landmarks", type=str, default=None,
+                   help=".npy (68,2): the face landmarks of the first frame, for --scale_image (replaces the dlib pass)")
+    p.add_argument("--scale_on", choices=["gpu", "host"], default="gpu",
+                   help="--scale_image: filter, resize and crop frames on the GPU (one kernel per batch) or on the host with cv2")
     p.add_argument("--smooth_window", type=int, default=0,
                    help="N > 0 with --video: temporally smooth the parsing maps over 2N+1 frames first (smooth_parsing_map.py's "
                         "--window_size; the two-step workflow in one command); 0 = off")
@@ -150,26 +156,20 @@ class Cv2Sink:
 
 
 class FaceCrop:
-    """--scale_image (style_transfer.py:113-127,150-155): the first frame's eye distance fixes one resize + crop for the whole
-    video (util.py:163-188: 64 pixels between the eyes, --padding around their centre, multiples of 8); frames of a high-
+    """--scale_image --scale_on host (style_transfer.py:113-127,150-155): the first frame's eye distance fixes one resize + crop for
+    the whole video (util.py:163-188: 64 pixels between the eyes, --padding around their centre, multiples of 8); frames of a high-
     resolution source are low-pass filtered first ([1,3,3,1]/8 on both axes, once at scale <= 0.75, twice at <= 0.375).  The
-    landmarks are dlib's and the filter / resize are cv2's, exactly the calls the reference makes: without the two packages
-    this option stops with a message instead of approximating them."""
+    landmarks are dlib's (or --landmarks) and the filter / resize are cv2's, exactly the calls the reference makes, per frame on
+    the host: without cv2 this path stops with a message.  The default, --scale_on gpu, is vtoonify_amd/scale.py."""
 
-    def __init__(self, frame, bgr, padding):
+    def __init__(self, frame, bgr, padding, landmarks=None):
         try:
             import cv2
-            import dlib
         except ImportError:
-            raise SystemExit("--scale_image needs cv2 and dlib (face landmarks, util.py:get_video_crop_parameter); they are "
-                             "not importable here: pass frames that are already cropped") from None
-        from model.encoder.align_all_parallel import get_landmark        # the reference's helper, through the import mirror
+            raise SystemExit("--scale_image --scale_on host needs cv2 (sepFilter2D, resize); it is not importable here: use "
+                             "--scale_on gpu, or pass frames that are already cropped") from None
         self.cv2 = cv2
-        predictor = dlib.shape_predictor("./checkpoint/shape_predictor_68_face_landmarks.dat")
-        rgb = np.ascontiguousarray(frame[..., ::-1] if bgr else frame)
-        lm = get_landmark(rgb, predictor)
-        if lm is None:
-            raise SystemExit("--scale_image: no face found in the first frame")
+        lm = first_frame_landmarks(frame, bgr) if landmarks is None else landmarks
         eye_l, eye_r = lm[36:42], lm[42:48]
         self.scale = scale = 64.0 / (np.mean(eye_r[:, 0]) - np.mean(eye_l[:, 0]))
         cx, cy = ((np.mean(eye_r, axis=0) + np.mean(eye_l, axis=0)) / 2) * scale
@@ -187,6 +187,21 @@ class FaceCrop:
         if self.scale <= 0.375:
             frame = cv2.sepFilter2D(frame, -1, self.k, self.k)
         return cv2.resize(frame, (self.w, self.h))[self.top:self.bottom, self.left:self.right]
+
+
+def first_frame_landmarks(frame, bgr):
+    """The 68 dlib landmarks of the first frame (util.py:get_video_crop_parameter); --landmarks replaces this pass."""
+    try:
+        import dlib
+    except ImportError:
+        raise SystemExit("--scale_image needs the first frame's face landmarks: dlib is not importable here, pass "
+                         "--landmarks lm.npy (68,2), or frames that are already cropped") from None
+    from model.encoder.align_all_parallel import get_landmark        # the reference's helper, through the import mirror
+    predictor = dlib.shape_predictor("./checkpoint/shape_predictor_68_face_landmarks.dat")
+    lm = get_landmark(np.ascontiguousarray(frame[..., ::-1] if bgr else frame), predictor)
+    if lm is None:
+        raise SystemExit("--scale_image: no face found in the first frame")
+    return lm
 
 
 # ----------------------------------------------------------------------------------------- weights and style
@@ -294,9 +309,20 @@ def main(argv=None, device=None, backend=None) -> dict:
 
     # ---- style code: once per video, on rank 0 ----
     first = next(iter(src.frames(0, 1)))
-    crop = FaceCrop(first, src.bgr, opt.padding) if opt.scale_image else None       # parameters of the FIRST frame, for all
-    if crop is not None:
-        first = crop(first)
+    crop = prescale = None                                                          # parameters of the FIRST frame, for all
+    if opt.scale_image:
+        lm = None if opt.landmarks is None else np.load(opt.landmarks).reshape(68, 2)
+        if on_engine and opt.scale_on == "host":
+            crop = FaceCrop(first, src.bgr, opt.padding, lm)                        # the reference's cv2 calls, per frame
+        else:
+            from vtoonify_amd.scale import ScaleCrop, crop_parameters
+            lm = first_frame_landmarks(first, src.bgr) if lm is None else lm
+            sc = ScaleCrop(crop_parameters(lm, first.shape[:2], opt.padding), first.shape[0], first.shape[1])
+            if on_engine:
+                prescale = sc.to(device)                                            # one kernel per batch, in the video driver
+            else:
+                crop = sc.host                                                      # --cpu: the same arithmetic in numpy
+        first = prescale(first) if prescale is not None else crop(first)
     H, W = first.shape[0] // 8 * 8, first.shape[1] // 8 * 8                       # util.py:184-187 crops to //8*8
     s_w = style_code(opt, model, first, src.bgr, device, log) if rank == 0 else None
     d_s = opt.style_degree if opt.backbone == "dualstylegan" else None
@@ -341,7 +367,8 @@ def main(argv=None, device=None, backend=None) -> dict:
 
     def shard_source():
         for j, fr in enumerate(src.frames(a, b)):
-            fr = (fr if crop is None else crop(fr))[:H, :W]
+            if prescale is None:                          # (with a prescale the driver takes the source-size frame)
+                fr = (fr if crop is None else crop(fr))[:H, :W]
             yield fr, (None if maps is None else np.asarray(maps[a + j], dtype=np.float32)[:, :H, :W])
 
     def smoothed_source():
@@ -353,12 +380,12 @@ def main(argv=None, device=None, backend=None) -> dict:
 
         def feed():
             for j, fr in enumerate(src.frames(lo, hi)):
-                fr = fr if crop is None else crop(fr)
+                full, fr = fr, (prescale(fr) if prescale is not None else fr if crop is None else crop(fr))
                 if a <= lo + j < b:
-                    held.append(fr)
+                    held.append(full if prescale is not None else fr[:H, :W])
                 yield np.ascontiguousarray(fr)
         for p in smoother.smooth_shard(feed(), n, a, b):
-            yield held.popleft()[:H, :W], np.ascontiguousarray(p[0].cpu().numpy()[:, :H, :W])
+            yield held.popleft(), np.ascontiguousarray(p[0].cpu().numpy()[:, :H, :W])
 
     if smoother is not None:
         shard_source = smoothed_source
@@ -367,7 +394,7 @@ def main(argv=None, device=None, backend=None) -> dict:
     emit = (lambda i, fr: local.append(fr.copy())) if gather else sink
     if on_engine:
         vt = VideoToonifier(model.engine(), s_w, d_s, batch_size=opt.batch_size, bgr=src.bgr, depth=opt.depth,
-                            parsing_engine=None if par is None else par.engine())
+                            parsing_engine=None if par is None else par.engine(), prescale=prescale)
         done = vt.run(shard_source(), emit, first_index=a)
         if device.type == "cuda":
             torch.cuda.synchronize(device)

@@ -152,6 +152,13 @@ _PREPASS_SIGS = {
 }
 PREPASS_SYMBOLS = tuple(_PREPASS_SIGS)
 
+# include/vtoonify_amd_frames.h: --scale_image on the GPU (source-size frames), additive to ABI version 5
+_FRAMES_SIGS = {
+    "vt_frame_scale_crop": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                                               C.c_void_p]),
+}
+FRAMES_SYMBOLS = tuple(_FRAMES_SIGS)
+
 _lib = None
 _lib_path = None
 
@@ -163,7 +170,7 @@ def _bind(path: str):
     # "no ROCm-capable device is detected" at the first launch.)
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    for name, (res, args) in {**_SIGS, **_PREPASS_SIGS}.items():
+    for name, (res, args) in {**_SIGS, **_PREPASS_SIGS, **_FRAMES_SIGS}.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args

@@ -19,7 +19,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIBNAME = "libvtoonify_amd.so"
 SOURCES = ["capi.hip", "fused_bias_act.hip", "upfirdn2d.hip", "style_ops.hip", "conv_igemm.hip",
-           "norm_glue.hip", "frame_io.hip", "parsing_glue.hip", "raft_corr.hip", "flow_ops.hip"]
+           "norm_glue.hip", "frame_io.hip", "parsing_glue.hip", "raft_corr.hip", "flow_ops.hip", "frame_scale.hip"]
 ARCH = "gfx950"
 # -fno-slp-vectorize: hipcc's SLP vectoriser packs neighbouring fp32 operations into v_pk_{mul,add,fma}_f32 with lane selects;
 # the form `op_sel:[0,1]` (low result reads the HIGH register of src1) returns src1.hi as ZERO on gfx950 in ~1 % of executions
@@ -43,7 +43,8 @@ def lib_path() -> str:
 
 def _deps(src: str):
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
-    hdrs.append(os.path.join(os.path.dirname(HERE), "include", "vtoonify_amd.h"))
+    inc = os.path.join(os.path.dirname(HERE), "include")
+    hdrs += [os.path.join(inc, f) for f in sorted(os.listdir(inc)) if f.endswith(".h")]
     return [src] + hdrs
 
 

@@ -79,11 +79,13 @@ def _stream(t: torch.Tensor):
 class _Slot:
     """Staging buffers of one in-flight batch."""
 
-    def __init__(self, B, H, W, pc, device, lane=0, host_parsing=True):
+    def __init__(self, B, H, W, pc, device, lane=0, host_parsing=True, src_rows=0, src_w=0):
         cuda = device.type == "cuda"
         self.lane = lane
         self.compute = torch.cuda.Stream(device) if cuda else None
-        self.h_frames = torch.empty((B, H, W, 3), dtype=torch.uint8, pin_memory=cuda)
+        # with a prescale the source's row slabs are staged and uploaded instead of frames at the network's size
+        self.h_frames = torch.empty((B, H, W, 3) if not src_rows else (B, src_rows, src_w, 3), dtype=torch.uint8, pin_memory=cuda)
+        self.d_src = torch.zeros((B, src_rows, src_w, 3), dtype=torch.uint8, device=device) if src_rows else None
         self.h_parsing = (torch.empty((B, pc, H, W), dtype=torch.float32, pin_memory=cuda)
                           if pc and host_parsing else None)
         self.d_rgb = torch.empty((B, 3, H, W), dtype=torch.float32, device=device) if pc and not host_parsing else None
@@ -113,7 +115,7 @@ class VideoToonifier:
     are (4H,4W,3) uint8 in the same channel order."""
 
     def __init__(self, engine, style: torch.Tensor, d_s: Optional[float], batch_size: int = 4, bgr: bool = True,
-                 depth: int = 2, use_graph: bool = True, parsing_engine=None, parsing_channels: int = 19):
+                 depth: int = 2, use_graph: bool = True, parsing_engine=None, parsing_channels: int = 19, prescale=None):
         if batch_size < 1 or depth < 1:
             raise ValueError("batch_size and depth must be >= 1")
         self.engine, self.style, self.d_s = engine, style, d_s
@@ -122,6 +124,9 @@ class VideoToonifier:
         self.cuda = self.device.type == "cuda"
         self.use_graph = use_graph and self.cuda
         self.parsing_engine, self.parsing_channels = parsing_engine, parsing_channels
+        # vtoonify_amd.scale.ScaleCrop: run() takes SOURCE-size frames and the blur + resize + crop of --scale_image is the
+        # first launch of every batch (None: frames arrive at the network's size, nothing changes)
+        self.prescale = prescale
         self._slots: List[_Slot] = []
         self._geom = None
         if self.cuda:
@@ -135,7 +140,8 @@ class VideoToonifier:
         if self._geom != (H, W, pc, host_parsing):
             if H % 8 or W % 8:
                 raise _lib.VtError("frame height and width must be multiples of 8 (util.py:184-187)")
-            self._slots = [_Slot(self.B, H, W, pc, self.device, lane=i, host_parsing=host_parsing)
+            src = {} if self.prescale is None else {"src_rows": self.prescale.rows, "src_w": self.prescale.Ws}
+            self._slots = [_Slot(self.B, H, W, pc, self.device, lane=i, host_parsing=host_parsing, **src)
                            for i in range(self.depth)]
             self._geom = (H, W, pc, host_parsing)
         return self._slots
@@ -144,9 +150,10 @@ class VideoToonifier:
         """Upload, compute, download `n` staged frames of `slot` (asynchronous on CUDA)."""
         pc = 0 if slot.d_parsing is None else slot.d_parsing.shape[1]
         host_p = slot.h_parsing is not None
+        d_in = slot.d_frames if slot.d_src is None else slot.d_src
         if self.cuda:
             with torch.cuda.stream(self.copy_up):
-                slot.d_frames[:n].copy_(slot.h_frames[:n], non_blocking=True)
+                d_in[:n].copy_(slot.h_frames[:n], non_blocking=True)
                 if host_p:
                     slot.d_parsing[:n].copy_(slot.h_parsing[:n], non_blocking=True)
                 slot.ev_up.record(self.copy_up)
@@ -159,7 +166,7 @@ class VideoToonifier:
                 slot.h_out[:n].copy_(slot.d_out[:n], non_blocking=True)
                 slot.ev_down.record(self.copy_down)
         else:
-            slot.d_frames[:n].copy_(slot.h_frames[:n])
+            d_in[:n].copy_(slot.h_frames[:n])
             if host_p:
                 slot.d_parsing[:n].copy_(slot.h_parsing[:n])
             self._compute(slot, n, pc)
@@ -169,6 +176,8 @@ class VideoToonifier:
         # a ragged final batch (n < B) still runs the B-frame plan: one set of plan buffers and one hipGraph
         # per lane, no capture in the middle of the pipeline; rows n..B-1 are stale and never retired
         n = self.B
+        if slot.d_src is not None:
+            self.prescale.apply(slot.d_src, out=slot.d_frames)
         if slot.d_rgb is not None:
             # no parsing maps from the source: x_p = nearest_x0.5(BiSeNet(2 * bilinear_x2(x))[0]) on the
             # GPU (style_transfer.py:170-172); the /16 is vt_frame_pack's parsing_scale
@@ -184,7 +193,8 @@ class VideoToonifier:
     # -- public -----------------------------------------------------------------------------
     def run(self, source: Iterable[Tuple[np.ndarray, Optional[np.ndarray]]],
             sink: Callable[[int, np.ndarray], None], first_index: int = 0) -> int:
-        """source yields (frame (H,W,3) uint8, parsing (pc,H,W) float32 or None) in frame order;
+        """source yields (frame (H,W,3) uint8, parsing (pc,H,W) float32 or None) in frame order (with a `prescale` the frame
+        has the SOURCE's size (Hs,Ws,3) and H, W are the crop's: prescale.H, prescale.W);
         sink(index, frame (4H,4W,3) uint8) is called in frame order (the returned array is only
         valid during the call -- it is a view of a recycled pinned buffer).  Returns the number
         of frames processed."""
@@ -206,7 +216,9 @@ class VideoToonifier:
                     f0, p0 = batch[0]
                     host_p = p0 is not None or self.parsing_engine is None
                     pc = (0 if p0 is None else p0.shape[0]) if host_p else self.parsing_channels
-                    slots = self._slots_for(f0.shape[0], f0.shape[1], pc, host_p)
+                    ps = self.prescale
+                    H, W = (f0.shape[0], f0.shape[1]) if ps is None else (ps.H, ps.W)
+                    slots = self._slots_for(H, W, pc, host_p)
                     slot = slots[k % self.depth]
                     k += 1
                     if slot in pending:   # the ring is full: retire the oldest batch first
@@ -214,7 +226,7 @@ class VideoToonifier:
                     for j, (f, p) in enumerate(batch):
                         if f.shape != f0.shape or f.dtype != np.uint8:
                             raise _lib.VtError("all frames of a video must share one (H,W,3) uint8 shape")
-                        np.copyto(slot.n_frames[j], f)
+                        np.copyto(slot.n_frames[j], f if ps is None else ps.slab(f))
                         if pc and host_p:
                             np.copyto(slot.n_parsing[j], p, casting="same_kind")
                     slot.count, slot.first = len(batch), idx
