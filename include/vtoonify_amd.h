@@ -353,7 +353,8 @@ int vt_affine_apply(void* out, int ld_out, const void* x, int ld_x,
 /* Fusion glue (model/vtoonify.py:127, 259): out[p] = [skip(3) | zeros | f_e[p][:] * m[p]] with
  * per-pixel stride ld_out = header + c, header = 8, 16, ... channels (64 makes the consumer's
  * channel count a multiple of the direct-to-LDS K-step).  skip is NCHW fp32 (n,3,h,w); mask (n,h,w) fp32
- * (NULL = 1, the Toonify backbone, vtoonify.py:262). */
+ * (NULL = 1, the Toonify backbone, vtoonify.py:262).  ld_out = c: no header, out[p] = f_e[p][:] * m[p]
+ * (skip is not read and may be NULL). */
 int vt_fusion_pack(void* out, int ld_out, const void* f_e, int ld_e, const float* mask,
                    const float* skip, int n, int hw, int c, int dtype, vt_stream stream);
 
@@ -489,4 +490,6 @@ int vt_mfma_selftest(float* c, const void* a, const void* b, int dtype, vt_strea
 #include "vtoonify_amd_prepass.h"
 /* ... and those for source-size frames (--scale_image on the GPU). */
 #include "vtoonify_amd_frames.h"
+/* ... and those of the Fusion block without its packed operand. */
+#include "vtoonify_amd_fusion.h"
 #endif /* VTOONIFY_AMD_H */

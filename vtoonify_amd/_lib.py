@@ -159,6 +159,13 @@ _FRAMES_SIGS = {
 }
 FRAMES_SYMBOLS = tuple(_FRAMES_SIGS)
 
+# include/vtoonify_amd_fusion.h: the Fusion block without its packed operand, additive to ABI version 5
+_FUSION_SIGS = {
+    "vt_conv2d_gate": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_int32, C.c_void_p]),
+    "vt_conv2d_hdr": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+}
+FUSION_SYMBOLS = tuple(_FUSION_SIGS)
+
 _lib = None
 _lib_path = None
 
@@ -170,7 +177,7 @@ def _bind(path: str):
     # "no ROCm-capable device is detected" at the first launch.)
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    for name, (res, args) in {**_SIGS, **_PREPASS_SIGS, **_FRAMES_SIGS}.items():
+    for name, (res, args) in {**_SIGS, **_PREPASS_SIGS, **_FRAMES_SIGS, **_FUSION_SIGS}.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args

@@ -92,6 +92,10 @@ struct ConvArgs {
     int x3;             // vt_conv_desc.dtype == VT_F32X3: fp32 tensors, products as three bf16 MFMAs where the instance exists
     int blk_pm, blk_cn;  // decode_block_2d: pixel tiles x channel tiles of the block of tiles one XCD owns (0 = channel-major order)
     int stride_x, dil_x;  // horizontal stride / dilation (high halves of vt_conv_desc.stride / dil); stride / dil: vertical
+    // the thin kernels' Fusion forms (include/vtoonify_amd_fusion.h; conv_thin.hpp)
+    void* fem;          // vt_conv2d_gate: src1 * out written as (N, H, W, c0) rows of ld_fem elements, or NULL
+    const float* hdr;   // vt_conv2d_hdr: hdr_c fp32 NCHW planes in front of src0's channels, zeros up to hdr_pad channels
+    int ld_fem, hdr_c, hdr_pad;
 };
 
 // One geometry on both axes: the only form the specialised kernel families are written for.  Anything else runs the generic
@@ -3027,6 +3031,59 @@ extern "C" int vt_conv2d(const vt_conv_desc* d, vt_stream stream) {
     // the plan had no reduce pass to carry the statistics: append the stand-alone launch
     return vt_internal_instnorm_partial(a.stats_part, d->out, d->ld_out, d->n, d->out_h * d->out_w, d->cout,
                                         d->dtype == VT_F32X3 ? VT_F32 : d->dtype, stream);
+}
+
+// ---- include/vtoonify_amd_fusion.h: the Fusion block without its packed operand ----
+static int fusion_form_run(const vt_conv_desc* d, ConvArgs& a, const char* who, vt_stream stream) {
+    a.force_generic = d->tile_hint >= 1000000000 || !axes_equal(a);
+    const int64_t wsf = (d->splitk_ws && d->splitk_ws_bytes > VT_TICKET_BYTES) ? (d->splitk_ws_bytes - VT_TICKET_BYTES) / 4 : 0;
+    if (plan_of(d, a, wsf).kind != 6) {
+        vt_set_error("%s: the descriptor does not run on the thin-output kernels", who);
+        return VT_ERR_UNSUPPORTED;
+    }
+    return d->dtype == VT_F16    ? dispatch<f16_t>(a, d->tile_hint, wsf, stream)
+           : d->dtype == VT_BF16 ? dispatch<bf16_t>(a, d->tile_hint, wsf, stream)
+                                 : dispatch<float>(a, d->tile_hint, wsf, stream);
+}
+
+extern "C" int vt_conv2d_gate(const vt_conv_desc* d, void* fem, int32_t ld_fem, vt_stream stream) {
+    ConvArgs a;
+    const int rc = fill_args(d, a);
+    if (rc != VT_OK) return rc;
+    VT_REQUIRE(fem, "vt_conv2d_gate: null fem");
+    if (!(a.in_absdiff && d->kh == 3 && d->kw == 3 && d->pad == 1 && d->cout == 1 && d->phases == 1)) {
+        vt_set_error("vt_conv2d_gate: needs the gate's mask conv (in_absdiff, 3x3, pad 1, cout 1)");
+        return VT_ERR_UNSUPPORTED;
+    }
+    const int esz = (d->dtype == VT_F32 || d->dtype == VT_F32X3) ? 4 : 2;
+    VT_REQUIRE(ld_fem >= d->c0 && (int64_t)ld_fem * esz % 16 == 0 && (uintptr_t)fem % 16 == 0,
+               "vt_conv2d_gate: fem needs 16-byte aligned pixel rows of ld_fem >= c0 elements");
+    a.fem = fem;
+    a.ld_fem = ld_fem;
+    return fusion_form_run(d, a, "vt_conv2d_gate", stream);
+}
+
+extern "C" int vt_conv2d_hdr(const vt_conv_desc* d, const float* hdr_planes, int32_t hdr_c, int32_t hdr_pad, vt_stream stream) {
+    ConvArgs a;
+    const int rc = fill_args(d, a);
+    if (rc != VT_OK) return rc;
+    VT_REQUIRE(hdr_planes, "vt_conv2d_hdr: null planes");
+    const int kstep = 4 * ((d->dtype == VT_F32 || d->dtype == VT_F32X3) ? 4 : 8);   // channels per K step of the thin kernels
+    if (!(d->kh == 3 && d->kw == 3 && d->pad == 1 && d->cout <= 3 && d->phases == 1 && d->c1 == 0 && !a.in_absdiff && !a.in_scale &&
+          !a.in_shift)) {
+        vt_set_error("vt_conv2d_hdr: needs a 3x3, pad 1 conv of one source with cout <= 3");
+        return VT_ERR_UNSUPPORTED;
+    }
+    if (hdr_c < 0 || hdr_pad <= 0 || hdr_c > hdr_pad || hdr_pad % kstep != 0) {
+        vt_set_error("vt_conv2d_hdr: needs 0 <= hdr_c <= hdr_pad, hdr_pad a positive multiple of the K step (%d channels)", kstep);
+        return VT_ERR_UNSUPPORTED;
+    }
+    a.hdr = hdr_planes;
+    a.hdr_c = hdr_c;
+    a.hdr_pad = hdr_pad;
+    a.cin = d->c0 + hdr_pad;    // the weights' channel count: [header | src0]
+    a.K = a.taps * a.cin;
+    return fusion_form_run(d, a, "vt_conv2d_hdr", stream);
 }
 
 extern "C" int vt_conv2d_tile(const vt_conv_desc* d) {

@@ -60,7 +60,52 @@ __device__ __forceinline__ int thin_tile_of_block() {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
-template <typename T, int KS, int NB, bool PRO = false>   // KS = 3 (3x3, pad 1) or 1 (1x1); NB = weight fragments (16 virtual channels each)
+// EXT: the two forms of the Fusion block that need no packed operand (vt_conv2d_gate / vt_conv2d_hdr).
+//   TH_GATE  the mask conv also writes fem[n][p][c] = round_T(float(src1[n][p][c]) * mask[n][p]) for the pixels of its own tile: the
+//            mask values meet in LDS, and after one barrier all threads walk the tile's pixel rows in 16-byte vectors -- the
+//            operations of fusion_pack_kernel (unpack, fp32 multiply by the stored fp32 mask, pack16<T>) in its order: the same bits.
+//            The tile's f_E pixels were read as fragments by this workgroup moments earlier.
+//   TH_HDR   the K range is [hdr_c fp32 NCHW planes, each value rounded to T | zeros up to hdr_pad channels | src0's c0 channels]:
+//            what fusion_pack_kernel wrote as the header of the packed operand is formed in the fragment registers.  The K steps
+//            keep their order and their waves; header steps that hold no plane are all zero and are skipped (accumulators start at
+//            +0 and a sum of +-0 products leaves +0: no bit changes).
+constexpr int TH_GATE = 1, TH_HDR = 2;
+
+// this lane's fragment of header K-step ks for the patch pixel at plane offset `pix` (< 0: padding)
+template <typename T>
+__device__ __forceinline__ u128 thin_hdr_frag(const ConvArgs& p, int img, int64_t pix, int ks, int q) {
+    constexpr int VEC = 16 / (int)sizeof(T);
+    float f[VEC];
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) {
+        const int ch = ks * 4 * VEC + q * VEC + i;
+        f[i] = (pix >= 0 && ch < p.hdr_c) ? p.hdr[((int64_t)img * p.hdr_c + ch) * ((int64_t)p.H * p.W) + pix] : 0.0f;
+    }
+    return pack16<T>(f);
+}
+
+// fem rows of the tile's in-image pixels (TH_GATE): consecutive threads take consecutive 16-byte vectors of a pixel row
+template <typename T, int TW, int NT>
+__device__ __forceinline__ void thin_gate_fem(const ConvArgs& p, const float* mtile, int img, int y0, int x0, int tid) {
+    constexpr int VEC = 16 / (int)sizeof(T);
+    const int cvn = p.c0 / VEC;
+    const T* fe = (const T*)p.src1;
+    T* fem = (T*)p.fem;
+    for (int i = tid; i < TW * TW * cvn; i += NT) {
+        const int px = i / cvn, cv = i - px * cvn;
+        const int oy = px / TW, ox = px - oy * TW;
+        if (y0 + oy >= p.H || x0 + ox >= p.W) continue;
+        const int64_t pix = (int64_t)(img * p.H + y0 + oy) * p.W + x0 + ox;
+        const float m = mtile[px];
+        float f[VEC];
+        unpack16<T>(ld128(fe + pix * p.ld1 + cv * VEC), f);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) f[k] *= m;
+        st128(fem + pix * p.ld_fem + cv * VEC, pack16<T>(f));
+    }
+}
+
+template <typename T, int KS, int NB, bool PRO = false, int EXT = 0>   // KS = 3 (3x3, pad 1) or 1 (1x1); NB = weight fragments (16 virtual channels each)
 __global__ void __launch_bounds__(TH_NW * 64) conv_thin_kernel(const ConvArgs p) {
     constexpr int VEC = 16 / (int)sizeof(T);
     constexpr int KSTEP = 4 * VEC;                   // channels per MFMA K-step (lane group q owns VEC of them)
@@ -114,7 +159,27 @@ __global__ void __launch_bounds__(TH_NW * 64) conv_thin_kernel(const ConvArgs p)
     const u128 zero = u128{0u, 0u, 0u, 0u};
     const int nk = p.cin / KSTEP;
     if constexpr (!PRO) {
-        for (int k0 = wave; k0 < nk; k0 += TH_NW * UNR) {
+        int kfirst = wave, coff = 0;   // this wave's first K-step; channel of src0 that K-step 0 starts at
+        if constexpr (EXT == TH_HDR) {
+            const int nh = p.hdr_pad / KSTEP;                        // header K-steps
+            for (int ks = wave; ks * KSTEP < p.hdr_c; ks += TH_NW) {  // (header step 0 on wave 0, as on the packed tensor)
+                u128 fw[NB];
+#pragma unroll
+                for (int b = 0; b < NB; ++b) fw[b] = woff[b] >= 0 ? ld128(wg + woff[b] + ks * KSTEP) : zero;
+#pragma unroll
+                for (int f = 0; f < NF; ++f) {
+                    const int pp = f * 16 + l15;
+                    const int py = pp / PW, px = pp - py * PW;
+                    const int iy = y0 + py - (KS / 2), ix = x0 + px - (KS / 2);
+                    const u128 fa = thin_hdr_frag<T>(p, img, poff[f] >= 0 ? (int64_t)iy * p.W + ix : -1, ks, q);
+#pragma unroll
+                    for (int b = 0; b < NB; ++b) Mma<T>::run(acc[f][b], fw[b], fa);
+                }
+            }
+            kfirst = nh + ((wave - nh) % TH_NW + TH_NW) % TH_NW;     // the smallest ks >= nh with ks = wave (mod 4)
+            coff = p.hdr_pad;
+        }
+        for (int k0 = kfirst; k0 < nk; k0 += TH_NW * UNR) {
             u128 fa[UNR][NF], fw[UNR][NB];
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
@@ -124,7 +189,7 @@ __global__ void __launch_bounds__(TH_NW * 64) conv_thin_kernel(const ConvArgs p)
                 // (predicated loads are right HERE: hipcc batches them -- all NF * UNR are issued before the first wait -- and
                 // dead lanes fetch nothing; the unconditional-at-a-clamped-offset form measured 124 -> 145 us over the 7 launches)
 #pragma unroll
-                for (int f = 0; f < NF; ++f) fa[u][f] = (live && poff[f] >= 0) ? ld128(src + poff[f] + kb) : zero;
+                for (int f = 0; f < NF; ++f) fa[u][f] = (live && poff[f] >= 0) ? ld128(src + poff[f] + (kb - coff)) : zero;
 #pragma unroll
                 for (int b = 0; b < NB; ++b) fw[u][b] = (live && woff[b] >= 0) ? ld128(wg + woff[b] + kb) : zero;
             }
@@ -229,23 +294,33 @@ __global__ void __launch_bounds__(TH_NW * 64) conv_thin_kernel(const ConvArgs p)
     const int opix = tid & 63, co = tid >> 6;
     const int oy = opix / TH_TW, ox = opix - oy * TH_TW;
     const int gy = y0 + oy, gx = x0 + ox;
-    if (co >= p.coutT || gy >= p.H || gx >= p.W) return;
-    float s = 0.0f;
+    __shared__ float mtile[EXT == TH_GATE ? TH_TW * TH_TW : 1];
+    const bool owns = co < p.coutT && gy < p.H && gx < p.W;
+    if (EXT != TH_GATE && !owns) return;      // (the gate form keeps every thread for the barrier and the fem rows below)
+    if (owns) {
+        float s = 0.0f;
 #pragma unroll
-    for (int tap = 0; tap < TAPS; ++tap) {
-        const int ky = tap / KS, kx = tap - ky * KS;
-        const int pp = (oy + ky) * PW + ox + kx;        // patch pixel under this tap
-        float t = 0.0f;
+        for (int tap = 0; tap < TAPS; ++tap) {
+            const int ky = tap / KS, kx = tap - ky * KS;
+            const int pp = (oy + ky) * PW + ox + kx;        // patch pixel under this tap
+            float t = 0.0f;
 #pragma unroll
-        for (int w = 0; w < TH_NW; ++w) t += dpart[w][pp][tap * p.coutT + co];   // K-slices in wave order
-        s += t;
+            for (int w = 0; w < TH_NW; ++w) t += dpart[w][pp][tap * p.coutT + co];   // K-slices in wave order
+            s += t;
+        }
+        const float ga = p.gain_alpha * (p.alpha_dev ? p.alpha_dev[0] : 1.0f);
+        const float v = conv_finish(p, s, p.bias ? p.bias[co] : 0.0f, ga, p.slope);
+        const int64_t HoWo = (int64_t)p.H * p.W;
+        const int64_t off = ((int64_t)img * p.cout + co) * HoWo + (int64_t)gy * p.W + gx;
+        const float* rs = (const float*)p.resid;
+        const float r = post_act(p, v + (rs ? p.beta * rs[off] : 0.0f));
+        ((float*)p.out)[off] = r;
+        if constexpr (EXT == TH_GATE) mtile[opix] = r;   // (cout = 1: the mask value of the pixel, as stored)
     }
-    const float ga = p.gain_alpha * (p.alpha_dev ? p.alpha_dev[0] : 1.0f);
-    const float v = conv_finish(p, s, p.bias ? p.bias[co] : 0.0f, ga, p.slope);
-    const int64_t HoWo = (int64_t)p.H * p.W;
-    const int64_t off = ((int64_t)img * p.cout + co) * HoWo + (int64_t)gy * p.W + gx;
-    const float* rs = (const float*)p.resid;
-    ((float*)p.out)[off] = post_act(p, v + (rs ? p.beta * rs[off] : 0.0f));
+    if constexpr (EXT == TH_GATE) {
+        __syncthreads();
+        thin_gate_fem<T, TH_TW, TH_NW * 64>(p, mtile, img, y0, x0, tid);
+    }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -264,7 +339,7 @@ constexpr int TH16 = 16;
 constexpr int TH16_NW = 4;           // wavefronts of the 16 x 16 form: 6 pixel fragments each (21 of an 18 x 18 patch).  (8 waves of 3
                                     // fragments with two K steps in flight in the gate half measured 50 / 31 us against 47 / 27.)
 
-template <typename T, int KS, int NB, bool PRO = false>
+template <typename T, int KS, int NB, bool PRO = false, int EXT = 0>   // (EXT: the forms of the 8 x 8 kernel)
 __global__ void __launch_bounds__(TH16_NW * 64) conv_thin16_kernel(const ConvArgs p) {
     constexpr int VEC = 16 / (int)sizeof(T);
     constexpr int KSTEP = 4 * VEC;
@@ -342,8 +417,28 @@ __global__ void __launch_bounds__(TH16_NW * 64) conv_thin16_kernel(const ConvArg
         }
     };
     const int nk0 = (PRO && p.in_absdiff) ? p.c0 / KSTEP : nk;   // K steps that read src0 as it is
+    int kfirst = 0, coff = 0;
+    if constexpr (EXT == TH_HDR) {
+        // ---- header K steps: the fp32 planes (steps without a plane are all zero: skipped) ----
+        for (int ks = 0; ks * KSTEP < p.hdr_c; ++ks) {
+            u128 fw[NB];
+#pragma unroll
+            for (int b = 0; b < NB; ++b) fw[b] = woff[b] >= 0 ? ld128(wg + woff[b] + ks * KSTEP) : zero;
+#pragma unroll
+            for (int i = 0; i < FPW; ++i) {
+                const int pp = (wave + TH16_NW * i) * 16 + l15;
+                const int py = pp / PW, px = pp - py * PW;
+                const int iy = y0 + py - (KS / 2), ix = x0 + px - (KS / 2);
+                const u128 fa = thin_hdr_frag<T>(p, img, poff[i] >= 0 ? (int64_t)iy * p.W + ix : -1, ks, q);
+#pragma unroll
+                for (int b = 0; b < NB; ++b) Mma<T>::run(acc[i][b], fw[b], fa);
+            }
+        }
+        kfirst = p.hdr_pad / KSTEP;
+        coff = p.hdr_pad;
+    }
     // ---- K steps [0, nk0): one source ----
-    for (int k0 = 0; k0 < nk0; k0 += UNR) {
+    for (int k0 = kfirst; k0 < nk0; k0 += UNR) {
         u128 fa[UNR][FPW], fw[UNR][NB];
         float scv[UNR][PRO ? VEC : 1], shv[UNR][PRO ? VEC : 1];
 #pragma unroll
@@ -351,7 +446,7 @@ __global__ void __launch_bounds__(TH16_NW * 64) conv_thin16_kernel(const ConvArg
             const bool live = k0 + u < nk0;
             const int kb = (live ? k0 + u : k0) * KSTEP;
 #pragma unroll
-            for (int i = 0; i < FPW; ++i) fa[u][i] = (live && poff[i] >= 0) ? ld128(src + poff[i] + kb) : zero;
+            for (int i = 0; i < FPW; ++i) fa[u][i] = (live && poff[i] >= 0) ? ld128(src + poff[i] + (kb - coff)) : zero;
             if (PRO) table(live ? k0 + u : k0, scv[u], shv[u]);
 #pragma unroll
             for (int b = 0; b < NB; ++b) fw[u][b] = (live && woff[b] >= 0) ? ld128(wg + woff[b] + kb) : zero;
@@ -415,23 +510,32 @@ __global__ void __launch_bounds__(TH16_NW * 64) conv_thin16_kernel(const ConvArg
     }
     __syncthreads();
     // stencil + epilogue: thread = output pixel, all of its (<= 3) channels
-    if (tid >= TH16 * TH16) return;
+    __shared__ float mtile[EXT == TH_GATE ? TH16 * TH16 : 1];
     const int oy = tid / TH16, ox = tid - oy * TH16;
     const int gy = y0 + oy, gx = x0 + ox;
-    if (gy >= p.H || gx >= p.W) return;
-    const float ga = p.gain_alpha * (p.alpha_dev ? p.alpha_dev[0] : 1.0f);
-    const int64_t HoWo = (int64_t)p.H * p.W;
-    const float* rs = (const float*)p.resid;
-    for (int co = 0; co < p.coutT; ++co) {
-        float s = 0.0f;
+    const bool owns = tid < TH16 * TH16 && gy < p.H && gx < p.W;
+    if (EXT != TH_GATE && !owns) return;      // (the gate form keeps every thread for the barrier and the fem rows below)
+    if (owns) {
+        const float ga = p.gain_alpha * (p.alpha_dev ? p.alpha_dev[0] : 1.0f);
+        const int64_t HoWo = (int64_t)p.H * p.W;
+        const float* rs = (const float*)p.resid;
+        for (int co = 0; co < p.coutT; ++co) {
+            float s = 0.0f;
 #pragma unroll
-        for (int tap = 0; tap < TAPS; ++tap) {
-            const int ky = tap / KS, kx = tap - ky * KS;
-            s += dt[(oy + ky) * PW + ox + kx][tap * p.coutT + co];
+            for (int tap = 0; tap < TAPS; ++tap) {
+                const int ky = tap / KS, kx = tap - ky * KS;
+                s += dt[(oy + ky) * PW + ox + kx][tap * p.coutT + co];
+            }
+            const float v = conv_finish(p, s, p.bias ? p.bias[co] : 0.0f, ga, p.slope);
+            const int64_t off = ((int64_t)img * p.cout + co) * HoWo + (int64_t)gy * p.W + gx;
+            const float r = post_act(p, v + (rs ? p.beta * rs[off] : 0.0f));
+            ((float*)p.out)[off] = r;
+            if constexpr (EXT == TH_GATE) mtile[tid] = r;   // (cout = 1: the mask value of the pixel, as stored)
         }
-        const float v = conv_finish(p, s, p.bias ? p.bias[co] : 0.0f, ga, p.slope);
-        const int64_t off = ((int64_t)img * p.cout + co) * HoWo + (int64_t)gy * p.W + gx;
-        ((float*)p.out)[off] = post_act(p, v + (rs ? p.beta * rs[off] : 0.0f));
+    }
+    if constexpr (EXT == TH_GATE) {
+        __syncthreads();
+        thin_gate_fem<T, TH16, TH16_NW * 64>(p, mtile, img, y0, x0, tid);
     }
 }
 
@@ -455,6 +559,29 @@ int launch_thin(const ConvArgs& a, vt_stream stream) {
     if ((a.in_scale || a.in_absdiff) && (a.taps != 9 || two)) {   // the loader prologue: only the Fusion gate's shape is compiled
         vt_set_error("vt_conv2d: in_scale / in_absdiff on a thin conv need a 3x3 kernel with 9 * cout <= 16");
         return VT_ERR_UNSUPPORTED;
+    }
+    // the forms without a packed fusion operand (vt_conv2d_gate / vt_conv2d_hdr, which have checked the shape): the same tiles
+    if (a.fem) {
+        if (thin16_wanted(a)) {
+            const unsigned b16 = (unsigned)((int64_t)a.N * vt_cdiv(a.H, TH16) * vt_cdiv(a.W, TH16));
+            auto k = conv_thin16_kernel<T, 3, 1, true, TH_GATE>;
+            VT_LAUNCH(k, dim3(b16), dim3(TH16_NW * 64), stream, args);
+            return vt_check_launch("vt_conv2d_gate(thin, 16x16)");
+        }
+        auto k = conv_thin_kernel<T, 3, 1, true, TH_GATE>;
+        VT_LAUNCH(k, dim3((unsigned)blocks), dim3(TH_NW * 64), stream, args);
+        return vt_check_launch("vt_conv2d_gate(thin)");
+    }
+    if (a.hdr_pad) {   // (two weight fragments for every cout <= 3: with 9 virtual channels the second one holds zeros)
+        if (thin16_wanted(a)) {
+            const unsigned b16 = (unsigned)((int64_t)a.N * vt_cdiv(a.H, TH16) * vt_cdiv(a.W, TH16));
+            auto k = conv_thin16_kernel<T, 3, 2, false, TH_HDR>;
+            VT_LAUNCH(k, dim3(b16), dim3(TH16_NW * 64), stream, args);
+            return vt_check_launch("vt_conv2d_hdr(thin, 16x16)");
+        }
+        auto k = conv_thin_kernel<T, 3, 2, false, TH_HDR>;
+        VT_LAUNCH(k, dim3((unsigned)blocks), dim3(TH_NW * 64), stream, args);
+        return vt_check_launch("vt_conv2d_hdr(thin)");
     }
     if (thin16_wanted(a)) {
         const unsigned b16 = (unsigned)((int64_t)a.N * vt_cdiv(a.H, TH16) * vt_cdiv(a.W, TH16));

@@ -789,9 +789,9 @@ extern "C" int vt_affine_apply(void* out, int ld_out, const void* x, int ld_x,
 
 extern "C" int vt_fusion_pack(void* out, int ld_out, const void* f_e, int ld_e, const float* mask,
                               const float* skip, int n, int hw, int c, int dtype, vt_stream stream) {
-    VT_REQUIRE(out && f_e && skip, "vt_fusion_pack: null tensor");
-    VT_REQUIRE(n > 0 && hw > 0 && c > 0 && c % 8 == 0 && ld_out >= c + 8 && (ld_out - c) % 8 == 0,
-               "vt_fusion_pack: bad sizes (ld_out = header + c, header a multiple of 8, >= 8)");
+    VT_REQUIRE(out && f_e && (skip || ld_out == c), "vt_fusion_pack: null tensor");
+    VT_REQUIRE(n > 0 && hw > 0 && c > 0 && c % 8 == 0 && (ld_out == c || ld_out >= c + 8) && (ld_out - c) % 8 == 0,
+               "vt_fusion_pack: bad sizes (ld_out = header + c, header a multiple of 8, >= 8, or no header)");
     if (dtype == VT_F32) {
         const int64_t total = (int64_t)n * hw * (ld_out / 4);
         auto k = fusion_pack_kernel<float>;

@@ -35,9 +35,10 @@ from ._lib import ACT_LRELU, ACT_NONE, ACT_RELU_TANH, OUT_NCHW, OUT_NHWC
 SQRT2 = math.sqrt(2.0)
 N_LATENT = 18
 _DIL = {1: 4, 2: 4, 3: 2, 4: 2, 5: 1, 6: 1}  # model/vtoonify.py:201-207
-# header of the fusion operand [skip(3) | zeros | f_E * m_E]: 64 channels so that the fusion_skip conv
-# (Cin = header + C) has a channel count the direct-to-LDS / patch kernels accept
-FEM_HDR = 64
+# header of fusion_skip's K range [skip(3) | zeros | f_E * m_E]: 64 channels, the layout of its packed weights (a whole number
+# of K steps in every type).  The fused gate (VToonifyEngine(fused_gate=True), the default) forms the header in the conv's
+# loader (vt_conv2d_hdr); only fused_gate=False still writes it to memory in front of f_E * m_E (vt_fusion_pack).
+SKIP_HDR = 64
 
 
 def _pad8(c: int) -> int:
@@ -73,7 +74,7 @@ class VToonifyEngine:
                  in_size: int = 256, dtype: torch.dtype = torch.bfloat16,
                  device: Optional[torch.device] = None, cache_styles: bool = False,
                  tile_hints: Optional[Dict[str, int]] = None, style_gate: bool = False, x3: bool = False,
-                 fuse_rgb128: bool = True):
+                 fuse_rgb128: bool = True, fused_gate=True):
         assert backbone in ("dualstylegan", "toonify")
         assert dtype in (torch.bfloat16, torch.float16, torch.float32)
         self.backbone = backbone
@@ -96,6 +97,14 @@ class VToonifyEngine:
             raise _lib.VtError("VToonifyEngine needs a GPU device (no CPU path)")
         self.cache_styles = cache_styles
         self.fuse_rgb128 = bool(fuse_rgb128)
+        # fused_gate: the Fusion levels without the packed operand [skip | zeros | f_E * m_E]: the mask conv writes
+        # f_E * m_E itself (vt_conv2d_gate) and fusion_skip reads the skip planes as a second source (vt_conv2d_hdr).  Bit-identical
+        # to `fused_gate=False`, which keeps the vt_fusion_pack launch and the 64-channel header for A/B measurements and tests.
+        # True fuses a level where that measured faster (profiles/fusion_gate_fem.txt): every level without a mask (Toonify: the pack
+        # pass just disappears), from 8192 pixels per image up with one (the mask conv's re-read of f_E and the header formed in
+        # the loader cost what the pack pass took at 64^2 and below: 39.1 against 39.0 us, 32.8 against 32.2).  "all": every level
+        # (tests, A/B).  Both forms give the same bits, so the rule is free to look at the geometry.
+        self.fused_gate = fused_gate if fused_gate == "all" else bool(fused_gate)
         # style_gate: the style path is skipped ON THE DEVICE when the W+ rows and d_s of a call equal the ones its
         # products were computed from (vt_style_gate: a bitwise compare in the frame's graph, no host sync) -- what the
         # video loop's `s_w.repeat(B,1,1)` (style_transfer.py:176: a new tensor per call, same content) needs; the
@@ -166,9 +175,9 @@ class VToonifyEngine:
                 self.w[f"fusion_out.{fi}"] = K.pack_conv_weight(sd[f"fusion_out.{fi}.weight"], out_dtype=T)
             wsk = sd[f"fusion_skip.{fi}.weight"]  # (3, C+3, 3, 3): cat[skip(3), f_E(*m)]
             c = wsk.shape[1] - 3
-            cmap = torch.tensor([0, 1, 2] + [-1] * (FEM_HDR - 3) + list(range(3, c + 3)), dtype=torch.int32,
+            cmap = torch.tensor([0, 1, 2] + [-1] * (SKIP_HDR - 3) + list(range(3, c + 3)), dtype=torch.int32,
                                 device=self.device)
-            self.w[f"fusion_skip.{fi}"] = K.pack_conv_weight(wsk, cin_dst=c + FEM_HDR, chan_map=cmap, out_dtype=T)
+            self.w[f"fusion_skip.{fi}"] = K.pack_conv_weight(wsk, cin_dst=c + SKIP_HDR, chan_map=cmap, out_dtype=T)
         # modulated conv weights stay fp32 (cout, cin, k, k); they are re-modulated per style
         self.modw = {}
         for i in range(6, 16):
@@ -223,8 +232,9 @@ class VToonifyEngine:
             d.tile_hint = int(h)
         return d
 
-    def _op_conv(self, ops, plan, ref_macs=None, branch=0, join=False, **kw):
-        """Append one vt_conv2d launch.  The op's info records the kernel instance (tile) and
+    def _op_conv(self, ops, plan, ref_macs=None, branch=0, join=False, entry=None, **kw):
+        """Append one vt_conv2d launch -- or one of `entry` = (function, arguments after the descriptor, kernel-name suffix,
+        extra algorithmic bytes): the forms of include/vtoonify_amd_fusion.h, which run the same descriptor.  The op's info records the kernel instance (tile) and
         its ALGORITHMIC work: flops = 2 x the MACs of the reference contraction it replaces
         (`ref_macs` overrides that for the fused conv_transpose2d+blur form, whose polyphase
         filters do 4x the transposed conv's MACs), bytes = every operand read once + the
@@ -250,8 +260,11 @@ class VToonifyEngine:
             info["branch"] = branch
         if join:
             info["join"] = True
+        if entry is not None:
+            info["form"] = entry[2]
+            info["bytes"] += entry[3]
         plan.convs.append((d, info, ops, len(ops)))
-        ops.append((self.lib.vt_conv2d, (C.byref(d),), info))
+        ops.append((self.lib.vt_conv2d, (C.byref(d),), info) if entry is None else (entry[0], (C.byref(d),) + tuple(entry[1]), info))
 
     def _conv_kind(self, **kw) -> int:
         """Kernel family vt_conv2d would run this conv on (vt_conv2d_tile KIND; host query, no launch)."""
@@ -581,7 +594,11 @@ class VToonifyEngine:
             if lvl < self.n_fuse:
                 f_e, ce, he, we = feats[lvl]
                 assert (he, we) == (h, w) and ce == co, "encoder/generator size mismatch (H, W must be multiples of 8)"
-                fem = self._buf(plan, f"fem{lvl}", (B, h, w, co + FEM_HDR))
+                fused = bool(self.fused_gate) and (self.fused_gate == "all" or not self.dual or hw >= 8192)
+                hdr = 0 if fused else SKIP_HDR     # channels in front of f_E * m_E in the fusion operand
+                # fused, Toonify backbone (no mask): the operand IS f_E
+                fem = f_e if (fused and not self.dual) else self._buf(plan, f"fem{lvl}", (B, h, w, co + hdr))
+                packed = False
                 mask = None
                 if self.dual:
                     # Fusion.forward (vtoonify.py:122-128)
@@ -607,7 +624,12 @@ class VToonifyEngine:
                     gate_kw = dict(src0=out, c0=co, ld0=co, src1=f_e, c1=co, ld1=co, in_scale=sc, in_shift=sh, in_absdiff=1)
                     gl = os.environ.get("VT_GATE_LOADER", "1")
                     in_loader = (gl != "0" and (hw >= 4096 or gl == "2") and self._conv_kind(**gate_kw, **mask_kw) == 6)
-                    if in_loader:
+                    if in_loader and fused:
+                        # ... and writes f_E * m_E for the pixels of its tiles (vt_conv2d_gate): no pack pass over f_E
+                        self._op_conv(ops, plan, **gate_kw, **mask_kw, join=True,
+                                      entry=(lib.vt_conv2d_gate, (C.c_void_p(fem.data_ptr()), co), "+fem", B * hw * co * self.esz))
+                        packed = True
+                    elif in_loader:
                         self._op_conv(ops, plan, **gate_kw, **mask_kw)
                     else:
                         nrm = self._buf(plan, f"nrm{lvl}", (B, h, w, 2 * co))
@@ -619,22 +641,29 @@ class VToonifyEngine:
                                      "bytes": 4 * B * hw * co * self.esz}))
                         self._op_conv(ops, plan, src0=nrm, c0=2 * co, ld0=2 * co, **mask_kw)
                     plan.masks.append(mask)
-                ops.append((lib.vt_fusion_pack,
-                            (C.c_void_p(fem.data_ptr()), co + FEM_HDR, C.c_void_p(f_e.data_ptr()), co,
-                             C.c_void_p(mask.data_ptr() if mask is not None else 0), C.c_void_p(skip.data_ptr()),
-                             B, hw, co, dt),
-                            {"name": "fusion_pack", "kernel": "fusion_pack", "flops": 0, "join": True,
-                             "bytes": B * hw * (co * self.esz + (co + FEM_HDR) * self.esz + 16)}))
+                if fem is not f_e and not packed:
+                    # (fused: only behind the two-launch mask conv of the H/8 level -- f_E * m_E without a header, ld_out = C)
+                    ops.append((lib.vt_fusion_pack,
+                                (C.c_void_p(fem.data_ptr()), co + hdr, C.c_void_p(f_e.data_ptr()), co,
+                                 C.c_void_p(mask.data_ptr() if mask is not None else 0), C.c_void_p(skip.data_ptr()),
+                                 B, hw, co, dt),
+                                {"name": "fusion_pack", "kernel": "fusion_pack", "flops": 0, "join": True,
+                                 "bytes": B * hw * (co * self.esz + (co + hdr) * self.esz + (16 if hdr else 4))}))
                 fo = self._buf(plan, f"fout{lvl}", (B, h, w, co))
                 wkey = f"fusion_out.{lvl}.conv" if self.dual else f"fusion_out.{lvl}"
-                self._op_conv(ops, plan, src0=out, c0=co, ld0=co, src1=fem.data_ptr() + FEM_HDR * self.esz, c1=co,
-                              ld1=co + FEM_HDR, n=B, h=h, w=w, out_h=h, out_w=w, weight=self.w[wkey], cout=co, kh=3,
+                self._op_conv(ops, plan, src0=out, c0=co, ld0=co, src1=fem.data_ptr() + hdr * self.esz, c1=co,
+                              ld1=co + hdr, n=B, h=h, w=w, out_h=h, out_w=w, weight=self.w[wkey], cout=co, kh=3,
                               kw=3, pad=1, bias=sd[wkey + ".bias"], out=fo, ld_out=co)
                 sk2 = self._buf(plan, f"fskip{lvl}", (B, 3, h, w), f32)
-                self._op_conv(ops, plan, src0=fem, c0=co + FEM_HDR, ld0=co + FEM_HDR, n=B, h=h, w=w, out_h=h, out_w=w,
-                              weight=self.w[f"fusion_skip.{lvl}"], cout=3, kh=3, kw=3, pad=1,
-                              bias=sd[f"fusion_skip.{lvl}.bias"], out=sk2, ld_out=0, out_layout=OUT_NCHW,
-                              out_dtype=K.VT_F32, branch=1)
+                skip_kw = dict(n=B, h=h, w=w, out_h=h, out_w=w, weight=self.w[f"fusion_skip.{lvl}"], cout=3, kh=3, kw=3, pad=1,
+                               bias=sd[f"fusion_skip.{lvl}.bias"], out=sk2, ld_out=0, out_layout=OUT_NCHW,
+                               out_dtype=K.VT_F32, branch=1)
+                if fused:
+                    # the skip planes as a second source: [skip(3) | zeros | fem] is the conv's K range, not a tensor
+                    self._op_conv(ops, plan, src0=fem, c0=co, ld0=co, **skip_kw,
+                                  entry=(lib.vt_conv2d_hdr, (C.c_void_p(skip.data_ptr()), 3, SKIP_HDR), "+hdr", B * hw * 12))
+                else:
+                    self._op_conv(ops, plan, src0=fem, c0=co + hdr, ld0=co + hdr, **skip_kw)
                 out, skip = fo, sk2
             n1, n2, n3 = f"convs.{6 + 2 * lvl}", f"convs.{7 + 2 * lvl}", f"to_rgbs.{3 + lvl}"
             c1o = self.modw[n1].shape[0]
@@ -728,7 +757,7 @@ class VToonifyEngine:
                      3: "conv3x3_c32_kernel", 4: "conv_fullk_kernel", 5: "conv_upblur_kernel",
                      6: "conv_thin_kernel", 7: "conv_patchs2_kernel", 8: "conv_fullkw_kernel", 9: "conv_upblur_rows_kernel",
                      10: "conv_upflat_kernel"}[kind]
-            info["kernel"] = f"{kname}<{tname},{bm}x{bn}>"
+            info["kernel"] = f"{kname}<{tname},{bm}x{bn}>" + info.get("form", "")
             info["splitk"] = sk
             if sk > 1 and self.lib.vt_conv2d_splitk_mode(C.byref(d)) == 2:
                 # two-pass split-K as two plan ops (slices, reduce): each is one GPU kernel, so the

@@ -163,6 +163,20 @@ def conv2d(*, stream_of=None, **kw):
     _lib.check(_lib.lib().vt_conv2d(C.byref(d), _stream(t)), "vt_conv2d")
 
 
+def conv2d_gate(fem, ld_fem, *, stream_of=None, **kw):
+    """vt_conv2d_gate: the Fusion gate's mask conv (descriptor `kw`, in_absdiff form) that also writes fem = src1 * mask."""
+    d = make_conv_desc(**kw)
+    t = stream_of if stream_of is not None else (kw["out"] if isinstance(kw["out"], torch.Tensor) else kw["src0"])
+    _lib.check(_lib.lib().vt_conv2d_gate(C.byref(d), _ptr(fem), int(ld_fem), _stream(t)), "vt_conv2d_gate")
+
+
+def conv2d_hdr(hdr_planes, hdr_c, hdr_pad, *, stream_of=None, **kw):
+    """vt_conv2d_hdr: a thin 3x3 conv whose K range is [hdr_c fp32 planes | zeros up to hdr_pad | src0's channels]."""
+    d = make_conv_desc(**kw)
+    t = stream_of if stream_of is not None else (kw["out"] if isinstance(kw["out"], torch.Tensor) else kw["src0"])
+    _lib.check(_lib.lib().vt_conv2d_hdr(C.byref(d), _ptr(hdr_planes), int(hdr_c), int(hdr_pad), _stream(t)), "vt_conv2d_hdr")
+
+
 def pack_conv_weight(w: torch.Tensor, cin_dst=None, chan_map=None, scale=1.0, src_transposed=False,
                      out_dtype=torch.float32):
     """w: (cout, cin, kh, kw) fp32 (or (cin, cout, kh, kw) when src_transposed)."""
