@@ -492,4 +492,6 @@ int vt_mfma_selftest(float* c, const void* a, const void* b, int dtype, vt_strea
 #include "vtoonify_amd_frames.h"
 /* ... and those of the Fusion block without its packed operand. */
 #include "vtoonify_amd_fusion.h"
+/* ... and the fused ToRGB that up-samples the RGB skip itself. */
+#include "vtoonify_amd_rgbup.h"
 #endif /* VTOONIFY_AMD_H */

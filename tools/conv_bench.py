@@ -72,6 +72,9 @@ def main():
     ap.add_argument("--adain", type=int, default=0,
                     help="whole-K trunk convs: bit 0 = AdaIN consumer (in_tile_stats + in_gb), bit 1 = emit tile_stats, bit 2 = residual")
     ap.add_argument("--rgb", action="store_true", help="attach the fused ToRGB epilogue to the same-resolution convs")
+    ap.add_argument("--rgbup", type=int, default=0, metavar="ROUNDS",
+                    help="with --rgb: time [vt_upfirdn2d of the RGB skip + conv] against vt_conv2d_rgbup (the up-sampling in the "
+                    "ToRGB epilogue), alternating ROUNDS times in this process; rgb_only on the 32 -> 32 level as in the engine")
     ap.add_argument("--lib", default="", help="another build of the library (same-box A/B of two .so files)")
     ap.add_argument("--sweep", default="", help="VAR=a,b,c: time every shape under each value of an environment switch the "
                     "library reads per call (same process, same buffers: a same-box A/B)")
@@ -150,6 +153,37 @@ def main():
             print(f"{name:<28} rejected: {lib.vt_last_error().decode()}")
             continue
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if args.rgbup and d.rgb_weight:
+            k1 = torch.tensor([1.0, 3.0, 3.0, 1.0], device=dev)
+            fir = (torch.outer(k1, k1) / 16.0).contiguous()
+            lo = torch.randn(n, 3, ho // 2, wo // 2, device=dev)
+            if cout == 32:
+                d.rgb_only = 1
+            up_args = (C.c_void_p(rgbo.data_ptr()), C.c_void_p(lo.data_ptr()), C.c_void_p(fir.data_ptr()), n * 3, ho // 2, wo // 2,
+                       4, 4, 2, 2, 1, 1, 2, 1, 2, 1, K.VT_F32)
+            fold_args = (C.byref(d), C.c_void_p(lo.data_ptr()), C.c_void_p(fir.data_ptr()))
+
+            def two():
+                _lib.check(lib.vt_upfirdn2d(*up_args, st), "upfirdn2d")
+                _lib.check(lib.vt_conv2d(C.byref(d), st), "conv")
+
+            def one():
+                _lib.check(lib.vt_conv2d_rgbup(*fold_args, st), "rgbup")
+
+            def timed(f):
+                for _ in range(3):
+                    f()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(args.iters):
+                    f()
+                e1.record()
+                torch.cuda.synchronize()
+                return 1e3 * e0.elapsed_time(e1) / args.iters
+            for r in range(args.rgbup):
+                a, b = timed(two), timed(one)
+                print(f"{name:<28} tile {tile:>9d} round {r}: upfirdn2d + conv {a:8.1f} us   rgbup {b:8.1f} us   {b - a:+7.1f} us")
+            continue
         var, vals = (args.sweep.split("=")[0], args.sweep.split("=")[1].split(",")) if args.sweep else ("", [""])
         for val in vals * (2 if args.sweep else 1):   # a sweep runs twice round: drift shows as a difference between rounds
             if var:

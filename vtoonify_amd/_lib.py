@@ -166,6 +166,12 @@ _FUSION_SIGS = {
 }
 FUSION_SYMBOLS = tuple(_FUSION_SIGS)
 
+# include/vtoonify_amd_rgbup.h: the fused ToRGB that up-samples the RGB skip itself, additive to ABI version 5
+_RGBUP_SIGS = {
+    "vt_conv2d_rgbup": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+RGBUP_SYMBOLS = tuple(_RGBUP_SIGS)
+
 _lib = None
 _lib_path = None
 
@@ -177,7 +183,7 @@ def _bind(path: str):
     # "no ROCm-capable device is detected" at the first launch.)
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    for name, (res, args) in {**_SIGS, **_PREPASS_SIGS, **_FRAMES_SIGS, **_FUSION_SIGS}.items():
+    for name, (res, args) in {**_SIGS, **_PREPASS_SIGS, **_FRAMES_SIGS, **_FUSION_SIGS, **_RGBUP_SIGS}.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args

@@ -1592,6 +1592,52 @@ conv_patch_kernel(const ConvArgs p, const GldsArgs g) {
 }
 
 // ---------------------------------------------------------------------------------------
+// Upsample(skip) of the RGB skip path (model/stylegan/model.py:32-50: upfirdn2d, up 2, pad (2, 1), 4 x 4 FIR) formed inside a
+// fused-ToRGB epilogue (vt_conv2d_rgbup): upfirdn2d_tile's UP == 2 branch (upfirdn2d.hip) for ONE output pixel (Y, X).
+// There, with pad0 = 2: X0 = X - 2, kx0 = posmod(-X0, 2) = X & 1, the input column of tap kx0 is floordiv(X0 + kx0, 2) =
+// ((X + 1) >> 1) - 1 and tap kx0 + 2 reads the next one; rows alike.  Taps are the flipped FIR, a sample outside the lo-res
+// image is the VALUE 0.0f through its fmaf, the sum starts from 0.0f and runs in (ky, kx) ascending order: the same bits.
+// ---------------------------------------------------------------------------------------
+struct SkipUpArgs {
+    const float* lo;    // (N, 3, h, w) fp32 planes of the previous level
+    const float* fir;   // 4 x 4
+    int h, w;
+};
+// the 2 x 2 taps an output pixel of row parity py, column parity px sees: uw[2 jy + jx] = k[py + 2 jy][px + 2 jx], k = flipped FIR
+__device__ __forceinline__ void skipup_taps(const float* fir, int py, int px, float (&uw)[4]) {
+#pragma unroll
+    for (int jy = 0; jy < 2; ++jy)
+#pragma unroll
+        for (int jx = 0; jx < 2; ++jx) uw[2 * jy + jx] = fir[(3 - py - 2 * jy) * 4 + (3 - px - 2 * jx)];
+}
+// element offsets (clamped into the plane: always legal) and in-image flags of the 2 x 2 lo-res samples of output pixel (Y, X)
+__device__ __forceinline__ void skipup_window(int Y, int X, int h, int w, int (&off)[4], bool (&ok)[4]) {
+    const int r0 = ((Y + 1) >> 1) - 1, c0 = ((X + 1) >> 1) - 1;
+#pragma unroll
+    for (int jy = 0; jy < 2; ++jy)
+#pragma unroll
+        for (int jx = 0; jx < 2; ++jx) {
+            const int r = r0 + jy, c = c0 + jx;
+            ok[2 * jy + jx] = (unsigned)r < (unsigned)h && (unsigned)c < (unsigned)w;
+            const int rc = r < 0 ? 0 : (r >= h ? h - 1 : r), cc = c < 0 ? 0 : (c >= w ? w - 1 : c);
+            off[2 * jy + jx] = rc * w + cc;
+        }
+}
+// the optional last argument of a kernel that carries the form (a pack of none or one SkipUpArgs)
+template <typename... UP>
+__device__ __forceinline__ SkipUpArgs skipup_of(const UP&... up) {
+    static_assert(sizeof...(UP) <= 1, "no argument or one SkipUpArgs");
+    if constexpr (sizeof...(UP) == 1) return (up, ...);
+    else return SkipUpArgs{nullptr, nullptr, 0, 0};
+}
+__device__ __forceinline__ float skipup_value(const float (&v)[4], const bool (&ok)[4], const float (&uw)[4]) {
+    float a = 0.0f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) a = fmaf(ok[t] ? v[t] : 0.0f, uw[t], a);
+    return a;
+}
+
+// ---------------------------------------------------------------------------------------
 // 3x3, Cin = Cout = 32, stride 1: the 1024x1024 level of the generator (convs.15) -- 19 GFLOP on
 // 134 MB of activations, HBM-bound (144 flop/B < the 312 flop/B ridge).  Everything that is not
 // the activation stream is taken off the memory path:
@@ -1604,10 +1650,16 @@ conv_patch_kernel(const ConvArgs p, const GldsArgs g) {
 //     16 pixels (4x4 XOR swizzle of the 16-byte slots), feeding 2 MFMAs (16x16x32);
 //   * epilogue (bias, LeakyReLU, fused ToRGB) from registers.
 // ---------------------------------------------------------------------------------------
-template <typename T>
+// UPF (vt_conv2d_rgbup): the ToRGB epilogue adds Upsample(skip) formed HERE from the lo-res planes `u.lo` --
+// upfirdn2d_tile's UP == 2 branch (upfirdn2d.hip) operation for operation, the same bits -- instead of reading planes that
+// a launch of their own wrote; p.rgb_resid is not touched.  The form is the instance with a third kernel argument,
+// conv3x3_c32_kernel<T, SkipUpArgs>; conv3x3_c32_kernel<T> takes the arguments it always took and compiles to the code it was.
+template <typename T, typename... UP>
 __global__ void __launch_bounds__(256, 2)   // 2 waves per SIMD = 2 workgroups per CU (<= 256 registers)
-conv3x3_c32_kernel(const ConvArgs p, const GldsArgs g) {
+conv3x3_c32_kernel(const ConvArgs p, const GldsArgs g, const UP... up) {
     static_assert(is_h16<T>::value, "16-bit operands only (64-byte pixel rows)");
+    constexpr bool UPF = sizeof...(UP) == 1;
+    const SkipUpArgs u = skipup_of(up...);
     constexpr int TH = 16, TW = 16, BM = 256, BN = 32, WM = 4, WN = 1;
     constexpr int TM = 4, TN = 2;
     constexpr int PH = TH + 2, PW = TW + 2, PROWS = PH * PW;   // 324 patch pixels
@@ -1690,6 +1742,11 @@ conv3x3_c32_kernel(const ConvArgs p, const GldsArgs g) {
     }
     float rb0 = 0.0f, rb1 = 0.0f, rb2 = 0.0f;
     if (rgbf && p.rgb_bias) rb0 = p.rgb_bias[0], rb1 = p.rgb_bias[1], rb2 = p.rgb_bias[2];
+    // UPF: the lane's ToRGB pixel is (y0 + 4 wm + q, x0 + l15) with y0, x0 multiples of 16, so the 2 x 2 of the 4 x 4 FIR it
+    // sees (skipup_taps) is the same for every tile: four registers for the life of the workgroup
+    static_assert(TH % 2 == 0 && TW % 2 == 0 && TM % 2 == 0, "the output parity of a lane's pixel does not depend on the tile");
+    float uw[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if constexpr (UPF) skipup_taps(u.fir, q & 1, l15 & 1, uw);
 
     int tile = blockIdx.x;
     if (tile >= ntiles) return;
@@ -1729,7 +1786,17 @@ conv3x3_c32_kernel(const ConvArgs p, const GldsArgs g) {
             const int im = mm / HoWo;
             o_rgb = (int64_t)im * 3 * HoWo + (mm - im * HoWo);
         }
-        if (rgbf && p.rgb_resid) {
+        float ulo[3][4];     // UPF: the 2 x 2 lo-res neighbourhood of the pixel, per plane -- twelve loads where the three were
+        bool uok[4];
+        if constexpr (UPF) {
+            int uoff[4];
+            skipup_window(y0 + wm * TM + q, x0 + l15, u.h, u.w, uoff, uok);
+            const float* lo = u.lo + (int64_t)img * 3 * u.h * u.w;
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+#pragma unroll
+                for (int t = 0; t < 4; ++t) ulo[j][t] = lo[j * (u.h * u.w) + uoff[t]];   // clamped address; masked where it is used
+        } else if (rgbf && p.rgb_resid) {
 #pragma unroll
             for (int j = 0; j < 3; ++j) rsd[j] = p.rgb_resid[o_rgb + (int64_t)j * HoWo];
         }
@@ -1785,6 +1852,10 @@ conv3x3_c32_kernel(const ConvArgs p, const GldsArgs g) {
             }
             if (rgbf) {
                 const float rr[3] = {racc[0], racc[1], racc[2]};   // lane (q, l15): pixel l15 of tile row q
+                if constexpr (UPF) {
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) rsd[j] = skipup_value(ulo[j], uok, uw);
+                }
                 if (m_rgb >= 0) {
                     p.rgb_out[o_rgb] = rr[0] + rb0 + rsd[0];
                     p.rgb_out[o_rgb + HoWo] = rr[1] + rb1 + rsd[1];
@@ -2647,7 +2718,7 @@ int launch_patchc(const ConvArgs& a, const GldsArgs& g, vt_stream stream) {
 
 // weights-resident persistent form (conv_patch_resident.hpp): one chunk of K, one channel tile, no split
 template <typename T, int TH, int BN>
-int launch_patchw(const ConvArgs& a, const GldsArgs& g, vt_stream stream) {
+int launch_patchw(const ConvArgs& a, const GldsArgs& g, vt_stream stream, const SkipUpArgs* su = nullptr) {
     ConvArgs args = a;
     args.slab_perm = ((BN / 16) % 2 == 0) ? 1 : 0;
     args.tiles_n = 1;
@@ -2658,13 +2729,18 @@ int launch_patchw(const ConvArgs& a, const GldsArgs& g, vt_stream stream) {
     int wgs = patchw_wgs();
     if (wgs > args.tiles_m) wgs = args.tiles_m;
     if (wgs >= 8) wgs &= ~7;                    // whole XCD rounds: the kernel hands out tiles per XCD
-    auto k = conv_patchw_kernel<T, TH, BN>;
+    if (su) {   // vt_conv2d_rgbup: Upsample(skip) in the ToRGB epilogue
+        void (*k)(const ConvArgs, const GldsArgs, const SkipUpArgs) = conv_patchw_kernel<T, TH, BN, SkipUpArgs>;
+        VT_LAUNCH(k, dim3((unsigned)wgs), dim3(512), stream, args, g, *su);
+        return vt_check_launch("vt_conv2d_rgbup(patch, weights resident)");
+    }
+    void (*k)(const ConvArgs, const GldsArgs) = conv_patchw_kernel<T, TH, BN>;
     VT_LAUNCH(k, dim3((unsigned)wgs), dim3(512), stream, args, g);
     return vt_check_launch("vt_conv2d(patch, weights resident)");
 }
 
 template <typename T>
-int launch_c32(const ConvArgs& a, const GldsArgs& g, vt_stream stream) {
+int launch_c32(const ConvArgs& a, const GldsArgs& g, vt_stream stream, const SkipUpArgs* su = nullptr) {
     ConvArgs args = a;
     args.slab_perm = 0;
     args.splitk = 1;
@@ -2677,18 +2753,31 @@ int launch_c32(const ConvArgs& a, const GldsArgs& g, vt_stream stream) {
         const int v = atoi(e);
         if (v > 0 && v < blocks) blocks = v;
     }
-    auto k = conv3x3_c32_kernel<T>;
+    if (su) {   // vt_conv2d_rgbup: Upsample(skip) in the ToRGB epilogue
+        void (*k)(const ConvArgs, const GldsArgs, const SkipUpArgs) = conv3x3_c32_kernel<T, SkipUpArgs>;
+        VT_LAUNCH(k, dim3((unsigned)blocks, (unsigned)groups), dim3(256), stream, args, g, *su);
+        return vt_check_launch("vt_conv2d_rgbup(c32)");
+    }
+    void (*k)(const ConvArgs, const GldsArgs) = conv3x3_c32_kernel<T>;
     VT_LAUNCH(k, dim3((unsigned)blocks, (unsigned)groups), dim3(256), stream, args, g);
     return vt_check_launch("vt_conv2d(c32)");
 }
 
+// su (vt_conv2d_rgbup): the launch must be one of the two forms that carry Upsample(skip) in their ToRGB epilogue -- the
+// persistent 32 -> 32 kernel or the weights-resident patch form -- or nothing is launched (VT_ERR_UNSUPPORTED)
 template <typename T>
-int dispatch(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) {
+int dispatch(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream, const SkipUpArgs* su = nullptr) {
     ConvArgs a = a0;
     a.force_generic = hint >= 1000000000 || !axes_equal(a);
     const TilePlan t = choose_plan<T>(a, hint % 1000000000, ws_floats);
     a.splitk = t.splitk;
     a.ldp = slab_ld(a.coutT);
+    if (su && t.kind != 3 && t.kind != 1) {
+        vt_set_error("vt_conv2d_rgbup: the descriptor runs on neither the persistent 32 -> 32 kernel nor the weights-resident "
+                     "patch form (plan kind %d)", t.kind);
+        return VT_ERR_UNSUPPORTED;
+    }
+
     if (a.rgb_w && (t.bn < a.coutT || t.splitk > 1)) {
         vt_set_error("vt_conv2d: fused ToRGB needs all %d output channels in one tile (plan %dx%d, split %d)",
                      a.coutT, t.bm, t.bn, t.splitk);
@@ -2795,7 +2884,7 @@ int dispatch(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) 
             vt_set_error("vt_conv2d: c32 kernel requested for an ineligible convolution");
             return VT_ERR_UNSUPPORTED;
         }
-        if constexpr (is_h16<T>::value) return launch_c32<T>(a, g, stream);   // (c32_eligible admits 16-bit operands only)
+        if constexpr (is_h16<T>::value) return launch_c32<T>(a, g, stream, su);   // (c32_eligible admits 16-bit operands only)
     }
     if (t.kind == 1 && a.transposed) {
         GldsArgs g;
@@ -2837,7 +2926,11 @@ int dispatch(const ConvArgs& a0, int hint, int64_t ws_floats, vt_stream stream) 
                 if (pipe && !(e && e[0] == '1') && a.dil == 1 && t.bm == 256 && t.bn == 64 && units == 1 && lean && !a.src1 &&
                     a.splitk <= 1 &&
                     (int64_t)(batch_exact() ? 1 : a.N) * vt_cdiv(a.Ho, 16) * vt_cdiv(a.Wo, 16) >= 2 * patchw_wgs())
-                    return launch_patchw<T, 16, 64>(a, g, stream);
+                    return launch_patchw<T, 16, 64>(a, g, stream, su);
+            }
+            if (su) {
+                vt_set_error("vt_conv2d_rgbup: the descriptor does not run on the weights-resident patch form (tile %dx%d)", t.bm, t.bn);
+                return VT_ERR_UNSUPPORTED;
             }
             // more tiles than CUs, whole K, lean epilogue: persistent workgroups, the pipeline runs across tile boundaries
             // (VT_PATCH_PIPE=1: one workgroup per tile, A/B).  VT_BATCH_EXACT or not: the same bits either way.
@@ -3084,6 +3177,28 @@ extern "C" int vt_conv2d_hdr(const vt_conv_desc* d, const float* hdr_planes, int
     a.cin = d->c0 + hdr_pad;    // the weights' channel count: [header | src0]
     a.K = a.taps * a.cin;
     return fusion_form_run(d, a, "vt_conv2d_hdr", stream);
+}
+
+// ---- include/vtoonify_amd_rgbup.h: Upsample(skip) inside the fused-ToRGB epilogue ----
+extern "C" int vt_conv2d_rgbup(const vt_conv_desc* d, const float* lo_planes, const float* fir, vt_stream stream) {
+    ConvArgs a;
+    const int rc = fill_args(d, a);
+    if (rc != VT_OK) return rc;
+    VT_REQUIRE(lo_planes && fir, "vt_conv2d_rgbup: null planes or FIR");
+    if (!a.rgb_w || a.stats_part) {
+        vt_set_error("vt_conv2d_rgbup: needs a conv with the fused ToRGB (rgb_weight) and without stats_part");
+        return VT_ERR_UNSUPPORTED;
+    }
+    if (d->out_h % 2 != 0 || d->out_w % 2 != 0) {
+        vt_set_error("vt_conv2d_rgbup: the output (%d x %d) is not twice a lo-res image", d->out_h, d->out_w);
+        return VT_ERR_UNSUPPORTED;
+    }
+    a.rgb_resid = nullptr;   // the planes the epilogue adds are formed from lo_planes
+    const SkipUpArgs su{lo_planes, fir, d->out_h / 2, d->out_w / 2};
+    const int64_t wsf = (d->splitk_ws && d->splitk_ws_bytes > VT_TICKET_BYTES) ? (d->splitk_ws_bytes - VT_TICKET_BYTES) / 4 : 0;
+    return d->dtype == VT_F16    ? dispatch<f16_t>(a, d->tile_hint, wsf, stream, &su)
+           : d->dtype == VT_BF16 ? dispatch<bf16_t>(a, d->tile_hint, wsf, stream, &su)
+                                 : dispatch<float>(a, d->tile_hint, wsf, stream, &su);
 }
 
 extern "C" int vt_conv2d_tile(const vt_conv_desc* d) {

@@ -17,11 +17,18 @@
 // 140 on the pipelined tiles: with every wave in its epilogue at the same time the matrix pipe idled for it.
 // LDS: 72 KB weights + 2 x 41 KB patches = 154 KB.  Tiles are handed out per XCD in contiguous ranges (neighbouring
 // tiles share halo rows in that XCD's L2).
+//
+// UPF (vt_conv2d_rgbup): the fused ToRGB adds Upsample(skip) formed in the E slot from the lo-res planes
+// (skipup_* in conv_igemm.hip: upfirdn2d_tile's operations, the same bits) -- twelve counted one-register loads where the
+// three skip loads are, p.rgb_resid untouched.  The form is conv_patchw_kernel<T, TH, BN, SkipUpArgs>, with a third kernel
+// argument; conv_patchw_kernel<T, TH, BN> takes the arguments it always took and compiles to the code it was.
 #pragma once
 
-template <typename T, int TH, int BN>
+template <typename T, int TH, int BN, typename... UP>
 __global__ void __launch_bounds__(512)
-conv_patchw_kernel(const ConvArgs p, const GldsArgs g) {
+conv_patchw_kernel(const ConvArgs p, const GldsArgs g, const UP... up) {
+    constexpr bool UPF = sizeof...(UP) == 1;
+    const SkipUpArgs u = skipup_of(up...);
     constexpr int TW = 16;
     constexpr int GW = 4;                                    // waves per group: one 16-pixel x TM-row block each
     constexpr int BM = TH * TW;
@@ -120,10 +127,16 @@ conv_patchw_kernel(const ConvArgs p, const GldsArgs g) {
     const int HoWo = p.Ho * p.Wo;
     // (the host checked that the three tensors are below 2 GB; a null skip reads as zeros)
     const BufRaw rout = vt_make_raw(p.out, (uint32_t)((int64_t)p.M * p.ld_out * ESZ));
-    const BufRaw rskip = vt_make_raw(p.rgb_resid, (uint32_t)((int64_t)p.N * 3 * HoWo * 4));
+    // (UPF: the lo-res planes, a quarter of that; a sample outside the image is an offset outside the descriptor: it reads 0.0f)
+    const BufRaw rskip = UPF ? vt_make_raw(u.lo, (uint32_t)((int64_t)p.N * 3 * u.h * u.w * 4))
+                             : vt_make_raw(p.rgb_resid, (uint32_t)((int64_t)p.N * 3 * HoWo * 4));
     const BufRaw rimg = vt_make_raw(p.rgb_out, (uint32_t)((int64_t)p.N * 3 * HoWo * 4));
 
     const int q = lane >> 4, l15 = lane & 15, l7 = lane & 7;
+    // UPF: the lane's ToRGB pixel is (ty0 + 4 wm + q, tx0 + l15), ty0 and tx0 multiples of 16: its 2 x 2 of the FIR never changes
+    static_assert(TH % 2 == 0 && TW % 2 == 0 && TM % 2 == 0, "the output parity of a lane's pixel does not depend on the tile");
+    float uw[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if constexpr (UPF) skipup_taps(u.fir, q & 1, l15 & 1, uw);
     uint32_t aswz[8][2];
 #pragma unroll
     for (int cm = 0; cm < 8; ++cm)
@@ -192,8 +205,10 @@ conv_patchw_kernel(const ConvArgs p, const GldsArgs g) {
         // that also drains the patch in flight: 154 us instead of 110 for the one-group form)
         // Every vector-memory operation of the slot is hidden from the compiler and COUNTED (vt_common.hpp): beside the LDS-DMA
         // in flight hipcc would wait vmcnt(0) at the first use of the skip pixels, and the slot would end by waiting for the
-        // acknowledgement of its own stores.  Order: patch pieces, [3 skip loads], 8 activation stores, [3 image stores]; the
+        // acknowledgement of its own stores.  Order: patch pieces, [3 skip loads; UPF: 12], 8 activation stores, [3 image stores]; the
         // wave leaves the slot when everything older than its stores has landed -- the patch, which is what the next M needs.
+        // (The fence counts what FOLLOWS the skip loads -- the 8 stores -- so it is the same for 3 and for 12 of them; at most
+        // PA + 12 + 8 + 3 operations of a wave are in flight, below vmcnt's 63.)
         if (j + 1 < ng) issue_patch(tile_of(j + 1));
         {
             const int tm = tile_of(j);
@@ -207,7 +222,21 @@ conv_patchw_kernel(const ConvArgs p, const GldsArgs g) {
                 o_rgb = (uint32_t)(ii * 3 * HoWo + (m_rgb - ii * HoWo)) * 4u;
             }
             u128 rsd[3];
-            if (rgbf) {
+            uint32_t ulo[3][4];
+            if constexpr (UPF) {
+                static_assert(PA + 12 + 2 * TM + 3 < 64, "vmcnt is 6 bits");
+                if (rgbf) {
+                    int uoff[4];
+                    bool uok[4];
+                    skipup_window(rowmap.y0 + wm * TM + q, rowmap.x0 + l15, u.h, u.w, uoff, uok);
+                    const int hw_lo = u.h * u.w;
+#pragma unroll
+                    for (int jc = 0; jc < 3; ++jc)
+#pragma unroll
+                        for (int t = 0; t < 4; ++t)
+                            vt_bload_hidden_u32(ulo[jc][t], rskip, uok[t] ? (uint32_t)((im * 3 + jc) * hw_lo + uoff[t]) * 4u : GLDS_OOB);
+                }
+            } else if (rgbf) {
 #pragma unroll
                 for (int jc = 0; jc < 3; ++jc) vt_bload_hidden<1>(rsd[jc], rskip, m_rgb >= 0 ? o_rgb + (uint32_t)(jc * HoWo) * 4u : GLDS_OOB);
             }
@@ -259,7 +288,14 @@ conv_patchw_kernel(const ConvArgs p, const GldsArgs g) {
 #pragma unroll
                 for (int jc = 0; jc < 3; ++jc) {
                     u128 o;
-                    o.x = vt_f2u((rr[jc] + rb[jc]) + vt_u2f(vt_settled(rsd[jc]).x)), o.y = o.z = o.w = 0u;
+                    if constexpr (UPF) {
+                        float skv = 0.0f;
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) skv = fmaf(vt_u2f(vt_settled_u32(ulo[jc][t])), uw[t], skv);
+                        o.x = vt_f2u((rr[jc] + rb[jc]) + skv), o.y = o.z = o.w = 0u;
+                    } else {
+                        o.x = vt_f2u((rr[jc] + rb[jc]) + vt_u2f(vt_settled(rsd[jc]).x)), o.y = o.z = o.w = 0u;
+                    }
                     vt_bstore_hidden<1>(rimg, m_rgb >= 0 ? o_rgb + (uint32_t)(jc * HoWo) * 4u : GLDS_OOB, o);
                 }
             } else {

@@ -567,6 +567,23 @@ __device__ __forceinline__ void vt_bstore_hidden(const BufRaw& r, uint32_t voff,
 #undef VT_BST
 }
 #endif
+// One hidden dword in ONE register (vt_bload_hidden<1> keeps a u128 per value: four registers once it is vt_settled) -- for the
+// twelve lo-res samples of conv_patchw's up-sampling ToRGB epilogue.  Same contract.
+#ifdef VT_EMU
+static inline void vt_bload_hidden_u32(uint32_t& v, const BufRaw& r, uint32_t voff) {
+    v = 0u;
+    if ((uint64_t)voff + 4 <= r.nrec) memcpy(&v, r.base + voff, 4);
+}
+static inline uint32_t vt_settled_u32(uint32_t v) { return v; }
+#else
+__device__ __forceinline__ void vt_bload_hidden_u32(uint32_t& v, const BufRaw& r, uint32_t voff) {
+    asm volatile("s_nop 4\n\tbuffer_load_dword %0, %1, %2, 0 offen" : "=&v"(v) : "v"(voff), "s"(r.v));
+}
+__device__ __forceinline__ uint32_t vt_settled_u32(uint32_t v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+#endif
 
 // wavefront (64 lanes) all-reduce sum via xor shuffles
 __device__ __forceinline__ float wave_sum(float v) {

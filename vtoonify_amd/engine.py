@@ -74,7 +74,7 @@ class VToonifyEngine:
                  in_size: int = 256, dtype: torch.dtype = torch.bfloat16,
                  device: Optional[torch.device] = None, cache_styles: bool = False,
                  tile_hints: Optional[Dict[str, int]] = None, style_gate: bool = False, x3: bool = False,
-                 fuse_rgb128: bool = True, fused_gate=True):
+                 fuse_rgb128: bool = True, fused_gate=True, fold_rgb_up: bool = True):
         assert backbone in ("dualstylegan", "toonify")
         assert dtype in (torch.bfloat16, torch.float16, torch.float32)
         self.backbone = backbone
@@ -105,6 +105,11 @@ class VToonifyEngine:
         # the loader cost what the pack pass took at 64^2 and below: 39.1 against 39.0 us, 32.8 against 32.2).  "all": every level
         # (tests, A/B).  Both forms give the same bits, so the rule is free to look at the geometry.
         self.fused_gate = fused_gate if fused_gate == "all" else bool(fused_gate)
+        # fold_rgb_up: at a level whose same-resolution conv carries the fused ToRGB on the persistent 32 -> 32 kernel or on the
+        # weights-resident patch form, that epilogue up-samples the previous level's RGB planes itself (vt_conv2d_rgbup,
+        # DESIGN.md 4.1x): no vt_upfirdn2d launch, and the hi-res planes are written once instead of written, read and
+        # rewritten.  Bit-identical to `fold_rgb_up=False`, which keeps the two launches for A/B measurements and tests.
+        self.fold_rgb_up = bool(fold_rgb_up)
         # style_gate: the style path is skipped ON THE DEVICE when the W+ rows and d_s of a call equal the ones its
         # products were computed from (vt_style_gate: a bitwise compare in the frame's graph, no host sync) -- what the
         # video loop's `s_w.repeat(B,1,1)` (style_transfer.py:176: a new tensor per call, same content) needs; the
@@ -275,6 +280,26 @@ class VToonifyEngine:
         d.splitk_ws, d.splitk_ws_bytes = 1 << 20, 1 << 40   # "a workspace will exist"
         tile = self.lib.vt_conv2d_tile(C.byref(d))
         return tile // 100000000 if tile >= 0 else -1
+
+    def _rgbup_resident(self, tile: int, n: int, ho: int, wo: int, cout: int) -> bool:
+        """Does a same-resolution conv with the fused ToRGB whose plan query returned `tile` run on the weights-resident patch
+        form (conv_patch_resident.hpp), the second form vt_conv2d_rgbup carries?  The launch rule of the library, from what
+        the query returns and the geometry: a 256 x 64 patch plan of a 64 -> 64 layer without split-K and at least two
+        16 x 16 tiles per persistent workgroup (VT_PATCH_PIPE, the library's A/B switch, moves both)."""
+        if os.environ.get("VT_PATCH_PIPE", "")[:1] in ("0", "1") or os.environ.get("VT_BATCH_EXACT", "")[:1] == "1":
+            return False
+        kind, sk, bm, bn = tile // 100000000, (tile // 1000000) % 100, (tile // 1000) % 1000, tile % 1000
+        return (kind == 1 and sk <= 1 and bm == 256 and bn == 64 and cout == 64 and
+                n * ((ho + 15) // 16) * ((wo + 15) // 16) >= 2 * self._patchw_wgs())
+
+    def _patchw_wgs(self) -> int:
+        """Persistent workgroups of the weights-resident form: one per compute unit (VT_PATCHW_WGS: the tests' override)."""
+        e = os.environ.get("VT_PATCHW_WGS", "")
+        if e.isdigit() and int(e) > 0:
+            return int(e)
+        if self.device.type == "cuda":
+            return torch.cuda.get_device_properties(self.device).multi_processor_count
+        return 256
 
     def _op_linear(self, ops, y, ld_y, x, ld_x, W, b, rows, w_scale=1.0, b_scale=1.0, act=ACT_NONE,
                    slope=0.2, gain=1.0):
@@ -670,17 +695,49 @@ class VToonifyEngine:
             up = self._buf(plan, f"up{lvl}", (B, 2 * h, 2 * w, c1o))
             o2 = self._buf(plan, f"gout{lvl}", (B, 2 * h, 2 * w, c1o))
             rgb = self._buf(plan, f"rgb{lvl}", (B, 3, 2 * h, 2 * w), f32)
-            # skip = Upsample(skip): upfirdn2d up=2 pad=(2,1) (model.py:32-50), fp32 planes
-            ops.append((lib.vt_upfirdn2d,
-                        (C.c_void_p(rgb.data_ptr()), C.c_void_p(skip.data_ptr()), C.c_void_p(self.fir_rgb.data_ptr()),
-                         B * 3, h, w, 4, 4, 2, 2, 1, 1, 2, 1, 2, 1, K.VT_F32),
-                        {"name": "upfirdn2d", "kernel": "upfirdn2d_tile<f32,up2>", "flops": 0, "branch": 1,
-                         "bytes": B * 3 * hw * 5 * 4}))
             groups = [(0, B)] if ns == 1 else [(b, 1) for b in range(B)]
+
+            def same_conv(b0, nb):
+                """The same-resolution StyledConv of frames b0 .. b0 + nb - 1: (descriptor arguments, ToRGB arguments, tile code of
+                the plan query with the ToRGB attached, ToRGB fused?, activation not stored?)"""
+                sidx = 0 if ns == 1 else b0
+                same_kw = dict(src0=up.data_ptr() + b0 * 4 * hw * c1o * self.esz, c0=c1o, ld0=c1o, n=nb,
+                               h=2 * h, w=2 * w, out_h=2 * h, out_w=2 * w, weight=plan.modw[n2][sidx], cout=c1o, kh=3, kw=3, pad=1,
+                               bias=sd[f"{g}{n2}.activate.bias"], act=ACT_LRELU, gain=SQRT2,
+                               out=o2.data_ptr() + b0 * 4 * hw * c1o * self.esz, ld_out=c1o)
+                rgb_ptr = rgb.data_ptr() + b0 * 3 * 4 * hw * 4
+                rgb_kw = dict(rgb_weight=plan.modw[n3][sidx], rgb_bias=self.w[f"{n3}.bias"], rgb_resid=rgb_ptr, rgb_out=rgb_ptr)
+                # ToRGB (1x1 modulated conv, no demod, + bias + up-sampled skip; model.py:383-392) is
+                # fused into the StyledConv's epilogue when one tile holds all its channels
+                probe = self._apply_hint(K.make_conv_desc(dtype=self.dt_conv, **same_kw, **rgb_kw))
+                probe.splitk_ws, probe.splitk_ws_bytes = 1 << 20, 1 << 40   # "a workspace will exist" (host query only)
+                tile = self.lib.vt_conv2d_tile(C.byref(probe))
+                fuse_rgb = tile >= 0 and tile % 1000 >= c1o and (tile // 1000000) % 100 <= 1
+                # (round 4 un-fused it on the 128-channel patch tiles in bf16, where the fused ToRGB had been sent back to the general
+                # epilogue after the wrong-image-row defect; with the cause found -- DESIGN.md 4.1n -- the lean / persistent kernels
+                # carry it again.  `fuse_rgb128=False` keeps round 4's two launches for A/B measurements.)
+                if fuse_rgb and not self.fuse_rgb128 and self.h16 and tile // 100000000 == 1 and tile % 1000 == 128:
+                    fuse_rgb = False
+                # the LAST level's activation feeds nothing but its ToRGB: with the fused epilogue on the persistent 32 -> 32
+                # kernel it is not stored at all (67 MB per 1024^2 frame; vt_conv_desc.rgb_only)
+                rgb_only = fuse_rgb and lvl == 4 and tile // 100000000 == 3
+                return same_kw, rgb_kw, tile, fuse_rgb, rgb_only
+
+            # The forms whose ToRGB epilogue up-samples the skip itself (vt_conv2d_rgbup): the persistent 32 -> 32 kernel and the
+            # weights-resident patch form.  Decided from the first group's plan: the groups of a level share geometry and batch.
+            _, _, tile0, fuse0, _ = same_conv(*groups[0])
+            fold_up = (self.fold_rgb_up and fuse0 and self.h16 and
+                       (tile0 // 100000000 == 3 or self._rgbup_resident(tile0, groups[0][1], 2 * h, 2 * w, c1o)))
+            if not fold_up:
+                # skip = Upsample(skip): upfirdn2d up=2 pad=(2,1) (model.py:32-50), fp32 planes
+                ops.append((lib.vt_upfirdn2d,
+                            (C.c_void_p(rgb.data_ptr()), C.c_void_p(skip.data_ptr()), C.c_void_p(self.fir_rgb.data_ptr()),
+                             B * 3, h, w, 4, 4, 2, 2, 1, 1, 2, 1, 2, 1, K.VT_F32),
+                            {"name": "upfirdn2d", "kernel": "upfirdn2d_tile<f32,up2>", "flops": 0, "branch": 1,
+                             "bytes": B * 3 * hw * 5 * 4}))
             for b0, nb in groups:
                 sidx = 0 if ns == 1 else b0
                 wm1 = plan.modw[n1][sidx]
-                wm2 = plan.modw[n2][sidx]
                 wm3 = plan.modw[n3][sidx]
                 # StyledConv(upsample): polyphase 3x3 with 4*Cout filters + pixel shuffle.
                 # Algorithmic MACs = the reference's conv_transpose2d (9 per in-pixel) + 4x4 blur
@@ -696,26 +753,15 @@ class VToonifyEngine:
                                   ld0=co, n=nb, h=h, w=w, out_h=h, out_w=w, weight=wm1, cout=c1o, kh=3, kw=3, pad=1,
                                   phases=4, bias=sd[f"{g}{n1}.activate.bias"], act=ACT_LRELU, gain=SQRT2,
                                   out=up.data_ptr() + b0 * 4 * hw * c1o * self.esz, ld_out=c1o)
-                same_kw = dict(src0=up.data_ptr() + b0 * 4 * hw * c1o * self.esz, c0=c1o, ld0=c1o, n=nb,
-                               h=2 * h, w=2 * w, out_h=2 * h, out_w=2 * w, weight=wm2, cout=c1o, kh=3, kw=3, pad=1,
-                               bias=sd[f"{g}{n2}.activate.bias"], act=ACT_LRELU, gain=SQRT2,
-                               out=o2.data_ptr() + b0 * 4 * hw * c1o * self.esz, ld_out=c1o)
-                rgb_ptr = rgb.data_ptr() + b0 * 3 * 4 * hw * 4
-                rgb_kw = dict(rgb_weight=wm3, rgb_bias=self.w[f"{n3}.bias"], rgb_resid=rgb_ptr, rgb_out=rgb_ptr)
-                # ToRGB (1x1 modulated conv, no demod, + bias + up-sampled skip; model.py:383-392) is
-                # fused into the StyledConv's epilogue when one tile holds all its channels
-                probe = self._apply_hint(K.make_conv_desc(dtype=self.dt_conv, **same_kw, **rgb_kw))
-                probe.splitk_ws, probe.splitk_ws_bytes = 1 << 20, 1 << 40   # "a workspace will exist" (host query only)
-                tile = self.lib.vt_conv2d_tile(C.byref(probe))
-                fuse_rgb = tile >= 0 and tile % 1000 >= c1o and (tile // 1000000) % 100 <= 1
-                # (round 4 un-fused it on the 128-channel patch tiles in bf16, where the fused ToRGB had been sent back to the general
-                # epilogue after the wrong-image-row defect; with the cause found -- DESIGN.md 4.1n -- the lean / persistent kernels
-                # carry it again.  `fuse_rgb128=False` keeps round 4's two launches for A/B measurements.)
-                if fuse_rgb and not self.fuse_rgb128 and self.h16 and tile // 100000000 == 1 and tile % 1000 == 128:
-                    fuse_rgb = False
-                # the LAST level's activation feeds nothing but its ToRGB: with the fused epilogue on the persistent 32 -> 32
-                # kernel it is not stored at all (67 MB per 1024^2 frame; vt_conv_desc.rgb_only)
-                rgb_only = fuse_rgb and lvl == 4 and tile // 100000000 == 3
+                same_kw, rgb_kw, tile, fuse_rgb, rgb_only = same_conv(b0, nb)
+                rgb_ptr = rgb_kw["rgb_out"]
+                if fold_up:
+                    # Upsample(skip) in the conv's ToRGB epilogue: the lo-res planes of this group's frames are its source
+                    lo_ptr = skip.data_ptr() + b0 * 3 * hw * 4
+                    self._op_conv(ops, plan, join=True, **same_kw, **rgb_kw, **({"rgb_only": 1} if rgb_only else {}),
+                                  entry=(lib.vt_conv2d_rgbup, (C.c_void_p(lo_ptr), C.c_void_p(self.fir_rgb.data_ptr())), ".up",
+                                         nb * 3 * hw * 4))
+                    continue
                 self._op_conv(ops, plan, join=fuse_rgb, **same_kw, **(rgb_kw if fuse_rgb else {}),
                               **({"rgb_only": 1} if rgb_only else {}))
                 if not fuse_rgb:

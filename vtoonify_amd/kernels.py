@@ -177,6 +177,13 @@ def conv2d_hdr(hdr_planes, hdr_c, hdr_pad, *, stream_of=None, **kw):
     _lib.check(_lib.lib().vt_conv2d_hdr(C.byref(d), _ptr(hdr_planes), int(hdr_c), int(hdr_pad), _stream(t)), "vt_conv2d_hdr")
 
 
+def conv2d_rgbup(lo_planes, fir, *, stream_of=None, **kw):
+    """vt_conv2d_rgbup: a conv with the fused ToRGB (descriptor `kw`) that adds Upsample(lo_planes) formed in its epilogue."""
+    d = make_conv_desc(**kw)
+    t = stream_of if stream_of is not None else (kw["out"] if isinstance(kw["out"], torch.Tensor) else kw["src0"])
+    _lib.check(_lib.lib().vt_conv2d_rgbup(C.byref(d), _ptr(lo_planes), _ptr(fir), _stream(t)), "vt_conv2d_rgbup")
+
+
 def pack_conv_weight(w: torch.Tensor, cin_dst=None, chan_map=None, scale=1.0, src_transposed=False,
                      out_dtype=torch.float32):
     """w: (cout, cin, kh, kw) fp32 (or (cin, cout, kh, kw) when src_transposed)."""
