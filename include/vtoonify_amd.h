@@ -494,4 +494,6 @@ int vt_mfma_selftest(float* c, const void* a, const void* b, int dtype, vt_strea
 #include "vtoonify_amd_fusion.h"
 /* ... and the fused ToRGB that up-samples the RGB skip itself. */
 #include "vtoonify_amd_rgbup.h"
+/* ... and the face alignment for the style encoder from given landmarks. */
+#include "vtoonify_amd_align.h"
 #endif /* VTOONIFY_AMD_H */

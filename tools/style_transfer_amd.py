@@ -23,9 +23,12 @@ serving image need not carry:
 `--scale_image` (the reference's resize + crop from the first frame's eye distance, util.py:163-188) runs on the GPU by default
 (`--scale_on gpu`: vtoonify_amd/scale.py, one kernel per batch over source-size frames) and needs only the first frame's 68
 face landmarks: `--landmarks lm.npy`, or dlib when it is importable.  `--scale_on host` is the reference's own per-frame cv2
-calls (FaceCrop below; needs cv2).  The aligned style crop needs dlib (model/encoder/align_all_parallel.py); without it pass
-either `--intrinsic_code` (the pSp encoder's (1,18,512) output, .npy) or accept
-the un-aligned first frame as the style encoder's input (a warning is printed).
+calls (FaceCrop below; needs cv2).  The aligned crop for the style encoder (model/encoder/align_all_parallel.py) is the
+reference's own function when dlib is importable; otherwise `--landmarks` also feeds the same alignment on the GPU
+(vtoonify_amd/align.py FaceAligner: Lanczos shrink, reflect pad with blur and median, quad transform; numpy with --cpu; with
+--scale_image the landmarks are mapped onto the scaled frame, where the reference would detect again).  With neither, pass
+`--intrinsic_code` (the pSp encoder's (1,18,512) output, .npy) or accept the un-aligned first frame as the style encoder's
+input (a message is printed).
 `--ckpt synthetic` / `--style_encoder_path synthetic` / `--faceparsing_path synthetic` build seeded random weights of the
 reference's schema (there are no checkpoints on the benchmark boxes); everything else is the reference's behaviour.
 """
@@ -82,7 +85,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--max_frames", type=int, default=None, help="stop after this many frames")
     p.add_argument("--seed", type=int, default=0, help="seed of `synthetic` weights")
     p.add_argument("--landmarks", type=str, default=None,
-                   help=".npy (68,2): the face landmarks of the first frame, for --scale_image (replaces the dlib pass)")
+                   help=".npy (68,2): the face landmarks of the first frame, for --scale_image and for the aligned crop of "
+                        "the style encoder (replaces the dlib passes).  With --scale_image the crop is aligned from these "
+                        "landmarks mapped onto the scaled frame (lm * scale - (left, top)); the reference detects them again "
+                        "on that frame")
     p.add_argument("--scale_on", choices=["gpu", "host"], default="gpu",
                    help="--scale_image: filter, resize and crop frames on the GPU (one kernel per batch) or on the host with cv2")
     p.add_argument("--smooth_window", type=int, default=0,
@@ -216,23 +222,36 @@ def load_generator_weights(opt, model):
     return torch.load(opt.ckpt, map_location="cpu")["g_ema"]            # style_transfer.py:63
 
 
-def style_code(opt, model, first_frame, bgr, device, log):
+def style_input(opt, first, bgr, device, log, lm=None):
+    """The pSp encoder's input (1,3,256,256) for the first frame (style_transfer.py:141,208): the reference's align_face when dlib
+    is importable; else, with the frame's 68 landmarks `lm` given, the same alignment from them (vtoonify_amd/align.py: kernels
+    on the engine, numpy with --cpu); else the un-aligned frame resized, with a message."""
+    face = first[..., ::-1] if bgr else first                                       # RGB
+    try:
+        import dlib  # noqa: F401
+        from model.encoder.align_all_parallel import align_face                     # the reference's own alignment, via the mirror
+        predictor = dlib.shape_predictor("./checkpoint/shape_predictor_68_face_landmarks.dat")
+        face = np.asarray(align_face(np.ascontiguousarray(face), predictor))
+    except ImportError:
+        if lm is not None:
+            from vtoonify_amd import align
+            face = np.ascontiguousarray(face)
+            if device.type == "cuda" or _lib.emulation_injected():
+                return align.FaceAligner(device)(face, lm)[1]
+            return torch.from_numpy(align.normalise_host(align.align_face_host(face, lm))).to(device)
+        log("[style] dlib / align_face not importable: the style encoder sees the un-aligned first frame resized to 256x256")
+    t = torch.from_numpy(np.ascontiguousarray(face)).to(device).permute(2, 0, 1)[None].float() / 255.0
+    return torch.nn.functional.interpolate((t - 0.5) / 0.5, size=(256, 256), mode="bilinear", align_corners=False)
+
+
+def style_code(opt, model, first_frame, bgr, device, log, lm=None):
     """W+ code of the video (style_transfer.py:135-147, 76-81): pSp on the (aligned) first frame -> zplus2wplus -> rows 0..6 from
     the extrinsic style (or all 18 with --color_transfer)."""
     if opt.intrinsic_code:
         z = torch.from_numpy(np.load(opt.intrinsic_code)).float().reshape(1, 18, 512).to(device)
     else:
         from vtoonify_amd.psp import GradualStyleEncoder
-        face = first_frame[..., ::-1] if bgr else first_frame                       # RGB
-        try:
-            import dlib  # noqa: F401
-            from model.encoder.align_all_parallel import align_face                 # the reference's own alignment, via the mirror
-            lm = dlib.shape_predictor("./checkpoint/shape_predictor_68_face_landmarks.dat")
-            face = np.asarray(align_face(np.ascontiguousarray(face), lm))
-        except ImportError:
-            log("[style] dlib / align_face not importable: the style encoder sees the un-aligned first frame resized to 256x256")
-        t = torch.from_numpy(np.ascontiguousarray(face)).to(device).permute(2, 0, 1)[None].float() / 255.0
-        t = torch.nn.functional.interpolate((t - 0.5) / 0.5, size=(256, 256), mode="bilinear", align_corners=False)
+        t = style_input(opt, first_frame, bgr, device, log, lm)
         dt = torch.float32 if device.type == "cpu" else torch.bfloat16
         psp = GradualStyleEncoder(50, "ir_se", compute_dtype=dt)
         if opt.style_encoder_path.startswith("synthetic"):
@@ -310,21 +329,26 @@ def main(argv=None, device=None, backend=None) -> dict:
     # ---- style code: once per video, on rank 0 ----
     first = next(iter(src.frames(0, 1)))
     crop = prescale = None                                                          # parameters of the FIRST frame, for all
+    lm = None if opt.landmarks is None else np.load(opt.landmarks).reshape(68, 2)
+    lm_first = None if lm is None else np.asarray(lm, dtype=np.float64)            # --landmarks, in the coordinates of `first`
     if opt.scale_image:
-        lm = None if opt.landmarks is None else np.load(opt.landmarks).reshape(68, 2)
         if on_engine and opt.scale_on == "host":
             crop = FaceCrop(first, src.bgr, opt.padding, lm)                        # the reference's cv2 calls, per frame
+            if lm_first is not None:
+                lm_first = lm_first * crop.scale - (crop.left, crop.top)
         else:
             from vtoonify_amd.scale import ScaleCrop, crop_parameters
             lm = first_frame_landmarks(first, src.bgr) if lm is None else lm
             sc = ScaleCrop(crop_parameters(lm, first.shape[:2], opt.padding), first.shape[0], first.shape[1])
+            if lm_first is not None:
+                lm_first = lm_first * sc.params.scale - (sc.params.left, sc.params.top)
             if on_engine:
                 prescale = sc.to(device)                                            # one kernel per batch, in the video driver
             else:
                 crop = sc.host                                                      # --cpu: the same arithmetic in numpy
         first = prescale(first) if prescale is not None else crop(first)
     H, W = first.shape[0] // 8 * 8, first.shape[1] // 8 * 8                       # util.py:184-187 crops to //8*8
-    s_w = style_code(opt, model, first, src.bgr, device, log) if rank == 0 else None
+    s_w = style_code(opt, model, first, src.bgr, device, log, lm=lm_first) if rank == 0 else None
     d_s = opt.style_degree if opt.backbone == "dualstylegan" else None
     if ws > 1:
         s_w, d = frames.broadcast_style(s_w, opt.style_degree, device)

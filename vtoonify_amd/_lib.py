@@ -172,6 +172,19 @@ _RGBUP_SIGS = {
 }
 RGBUP_SYMBOLS = tuple(_RGBUP_SIGS)
 
+# include/vtoonify_amd_align.h: face alignment for the style encoder from given landmarks, additive to ABI version 5
+_ALIGN_SIGS = {
+    "vt_align_resample_u8": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_int,
+                                                                                C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                                                C.c_void_p]),
+    "vt_align_pad_blend_workspace": (C.c_int64, [C.c_int] * 3),
+    "vt_align_pad_blend": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                                                              C.c_void_p]),
+    "vt_align_quad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int,
+                                C.c_void_p]),
+}
+ALIGN_SYMBOLS = tuple(_ALIGN_SIGS)
+
 _lib = None
 _lib_path = None
 
@@ -183,7 +196,8 @@ def _bind(path: str):
     # "no ROCm-capable device is detected" at the first launch.)
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    for name, (res, args) in {**_SIGS, **_PREPASS_SIGS, **_FRAMES_SIGS, **_FUSION_SIGS, **_RGBUP_SIGS}.items():
+    for name, (res, args) in {**_SIGS, **_PREPASS_SIGS, **_FRAMES_SIGS, **_FUSION_SIGS, **_RGBUP_SIGS,
+                              **_ALIGN_SIGS}.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
