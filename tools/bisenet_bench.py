@@ -4,7 +4,9 @@ at 512x512, style_transfer.py:171-172), HBM-resident, hipGraph replay, 1 and 3 f
 the CPU oracle timed beside it; and the video driver end to end with the maps computed on the GPU
 (uint8 frames in host memory -> uint8 1024x1024 frames in host memory, no parsing maps supplied).
 
-usage: python tools/bisenet_bench.py [--steps 100] [--no-cpu] [--no-video]"""
+--psp adds the style encoder's pass (1x3x256x256, hipGraph replay) in the same arithmetic.
+
+usage: python tools/bisenet_bench.py [--steps 100] [--dtype bf16|fp16|fp32] [--psp] [--no-cpu] [--no-video]"""
 import argparse
 import json
 import os
@@ -25,6 +27,8 @@ def keys(tag):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"], help="arithmetic of the networks")
+    ap.add_argument("--psp", action="store_true", help="also time the pSp style encoder (hipGraph replay)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-video", action="store_true")
     a = ap.parse_args()
@@ -34,8 +38,9 @@ def main():
     _lib.use_library(_lib.DEFAULT_LIB)
     dev = torch.device("cuda:0")
     bsd = synth.synth_state_dict(keys("bisenet"), 0)
-    par = BiSeNetEngine({k: v.to(dev) for k, v in bsd.items()}, 19, torch.bfloat16, dev)
-    res = {"what": "BiSeNet parsing maps, 3x256x256 frames -> net at 512x512 -> 19x256x256, bf16"}
+    dtype = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}[a.dtype]
+    par = BiSeNetEngine({k: v.to(dev) for k, v in bsd.items()}, 19, dtype, dev)
+    res = {"what": f"BiSeNet parsing maps, 3x256x256 frames -> net at 512x512 -> 19x256x256, {a.dtype}"}
     g = torch.Generator().manual_seed(0)
     for B in (1, 4):
         x = (torch.rand(B, 3, 256, 256, generator=g) * 2 - 1).to(dev)
@@ -53,9 +58,26 @@ def main():
             dt = time.perf_counter() - t0
             res[f"maps_per_s_b{B}_lanes{lanes}"] = a.steps * B / dt
             print(f"batch {B} lanes {lanes}: {a.steps * B / dt:8.1f} maps/s ({1e3 * dt / a.steps:.3f} ms/step)", flush=True)
+    if a.psp:
+        from vtoonify_amd.psp import PspEngine
+        psd = synth.synth_state_dict(keys("psp"), 0)
+        psp = PspEngine({k: v.to(dev) for k, v in psd.items()}, 18, dtype, dev)
+        xp = (torch.rand(1, 3, 256, 256, generator=g) * 2 - 1).to(dev)
+        for _ in range(3):
+            psp.forward(xp, use_graph=True)
+        torch.cuda.synchronize()
+        n = max(a.steps // 4, 5)
+        t0 = time.perf_counter()
+        for _ in range(n):
+            psp.forward(xp, use_graph=True)
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / n
+        res["psp_ms"] = 1e3 * dt
+        print(f"pSp 1x3x256x256 {a.dtype}, hipGraph replay: {1e3 * dt:.3f} ms per pass", flush=True)
+        del psp
     if not a.no_video:
         sd = synth.synth_state_dict(keys("D"), 0)
-        eng = VToonifyEngine({k: v.to(dev) for k, v in sd.items()}, "dualstylegan", 256, torch.bfloat16, dev)
+        eng = VToonifyEngine({k: v.to(dev) for k, v in sd.items()}, "dualstylegan", 256, dtype, dev)
         style = synth.synth_style(seed=17).to(dev)
         rng = np.random.default_rng(0)
         frames = rng.integers(0, 256, (8, 256, 256, 3), dtype=np.uint8)

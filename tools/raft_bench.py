@@ -23,14 +23,14 @@ def main():
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"],
+    ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "fp16"],
                     help="arithmetic of the convolutions (correlation lookup, GRU state exchange and flow stay fp32)")
     ap.add_argument("--pairs", type=int, default=0, help="frame pairs per call (default: the whole window, 2*window+1)")
     a = ap.parse_args()
     _lib.use_library(_lib.DEFAULT_LIB)
     dev = torch.device("cuda:0")
     m = RAFT(argparse.Namespace(small=False, mixed_precision=False, alternate_corr=False),
-             compute_dtype=torch.bfloat16 if a.dtype == "bf16" else torch.float32)
+             compute_dtype={"bf16": torch.bfloat16, "fp16": torch.float16}.get(a.dtype, torch.float32))
     m.load_state_dict(synth.synth_state_dict({k: tuple(v) for k, v in raft_schema().items()}, 0))
     m = m.to(dev).eval()
     wn, S = 2 * a.window + 1, a.size

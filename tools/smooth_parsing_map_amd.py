@@ -44,7 +44,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--video_path", type=str, help="path of the target video")
     p.add_argument("--output_path", type=str, default="./output/", help="path of the output parsing maps")
     # ---- additions of this driver ----
-    p.add_argument("--precision", choices=["fp32", "bf16"], default="fp32",
+    p.add_argument("--precision", choices=["fp32", "bf16", "fp16"], default="fp32",
                    help="arithmetic of RAFT and BiSeNet (fp32 = the reference's; the fusion is always fp32)")
     p.add_argument("--frame_order", choices=["bgr", "rgb"], default="bgr", help="channel order of .npy frames (cv2 files are BGR)")
     p.add_argument("--max_frames", type=int, default=None, help="stop after this many frames")
@@ -87,7 +87,7 @@ def main(argv=None, device=None) -> dict:
     device = torch.device("cuda", 0) if device is None else torch.device(device)
     src = open_source(opt.video_path, True, opt.frame_order)
     n = len(src) if opt.max_frames is None else min(len(src), opt.max_frames)
-    raft, par = load_models(opt, device, torch.bfloat16 if opt.precision == "bf16" else torch.float32)
+    raft, par = load_models(opt, device, {"bf16": torch.bfloat16, "fp16": torch.float16}.get(opt.precision, torch.float32))
     print("Load models successfully!", flush=True)
     sm = smooth.ParsingSmoother(raft, par, opt.window_size, iters=opt.iters, bgr=src.bgr)
     os.makedirs(opt.output_path, exist_ok=True)

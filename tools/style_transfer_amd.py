@@ -78,6 +78,9 @@ def build_parser() -> argparse.ArgumentParser:
     # ---- additions of this driver ----
     p.add_argument("--precision", choices=["fp32", "fp32_exact", "bf16", "fp16"], default=None,
                    help="arithmetic of the frame (default: VTOONIFY_AMD_DTYPE or fp32 = the reference's precision)")
+    p.add_argument("--aux_precision", choices=["bf16", "fp16", "fp32"], default=None,
+                   help="arithmetic of the parsing network and of the style encoder (default: the parsing network in the "
+                        "frame's precision, bf16 beside an fp16 frame, and the style encoder in bf16)")
     p.add_argument("--depth", type=int, default=3, help="batches in flight per GPU (each on its own stream and plan)")
     p.add_argument("--frame_order", choices=["bgr", "rgb"], default="bgr", help="channel order of .npy frames (cv2 files are BGR)")
     p.add_argument("--intrinsic_code", type=str, default=None,
@@ -96,6 +99,9 @@ def build_parser() -> argparse.ArgumentParser:
                         "--window_size; the two-step workflow in one command); 0 = off")
     p.add_argument("--raft_path", type=str, default="./checkpoint/raft-things.pth",
                    help="path of the RAFT model (smooth_parsing_map.py's option), used with --smooth_window")
+    p.add_argument("--smooth_precision", choices=["fp32", "bf16", "fp16"], default="fp32",
+                   help="arithmetic of RAFT and of the parsing network in the --smooth_window pre-pass (its fusion is always "
+                        "fp32); fp32 = smooth_parsing_map_amd.py's default")
     p.add_argument("--smooth_iters", type=int, default=20, help="RAFT iterations of --smooth_window (20 = smooth_parsing_map.py:154)")
     return p
 
@@ -252,7 +258,7 @@ def style_code(opt, model, first_frame, bgr, device, log, lm=None):
     else:
         from vtoonify_amd.psp import GradualStyleEncoder
         t = style_input(opt, first_frame, bgr, device, log, lm)
-        dt = torch.float32 if device.type == "cpu" else torch.bfloat16
+        dt = aux_dtype(opt) or (torch.float32 if device.type == "cpu" else torch.bfloat16)
         psp = GradualStyleEncoder(50, "ir_se", compute_dtype=dt)
         if opt.style_encoder_path.startswith("synthetic"):
             psp.load_state_dict(synth.synth_state_dict(_shapes("psp"), opt.seed))
@@ -278,6 +284,14 @@ def style_code(opt, model, first_frame, bgr, device, log, lm=None):
             else:
                 s_w[:, :7] = ex[:, :7]
     return s_w
+
+
+PRECISIONS = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
+
+
+def aux_dtype(opt):
+    """--aux_precision as a dtype, None when the option is not given."""
+    return PRECISIONS[opt.aux_precision] if getattr(opt, "aux_precision", None) else None
 
 
 def parsing_engine(opt, device, dtype):
@@ -363,12 +377,13 @@ def main(argv=None, device=None, backend=None) -> dict:
             raise SystemExit("--smooth_window needs --video on the GPU and excludes --parsing_map_path (it computes those maps)")
         import smooth_parsing_map_amd as spm
         from vtoonify_amd.smooth import ParsingSmoother
-        # the pre-pass in the arithmetic of its own command line's default (fp32), whatever the frame's precision: one
-        # command gives what smooth_parsing_map_amd.py followed by --parsing_map_path gives
-        raft, par_s = spm.load_models(opt, device, torch.float32)
+        # the pre-pass in the arithmetic of its own command line (--smooth_precision, default fp32 as there), whatever the
+        # frame's precision: one command gives what smooth_parsing_map_amd.py followed by --parsing_map_path gives
+        raft, par_s = spm.load_models(opt, device, PRECISIONS[opt.smooth_precision])
         smoother = ParsingSmoother(raft, par_s, opt.smooth_window, iters=opt.smooth_iters, bgr=src.bgr)
-    # (the parsing network has no fp16 form: it runs in bf16 beside an fp16 frame)
-    par = None if (maps is not None or smoother is not None) else parsing_engine(opt, device, torch.bfloat16 if cdt == torch.float16 else cdt)
+    # (without --aux_precision the parsing network runs in the frame's precision, in bf16 beside an fp16 frame)
+    par_dt = aux_dtype(opt) or (torch.bfloat16 if cdt == torch.float16 else cdt)
+    par = None if (maps is not None or smoother is not None) else parsing_engine(opt, device, par_dt)
 
     base = os.path.basename(opt.content.rstrip("/")).split(".")[0]
     stem = os.path.join(opt.output_path, f"{base}_vtoonify_{opt.backbone[0]}")
@@ -437,7 +452,8 @@ def main(argv=None, device=None, backend=None) -> dict:
     log(f"Transfer style successfully!  {n} frames in {dt:.2f} s ({n / max(dt, 1e-9):.1f} frames/s incl. I/O) -> {out_path}")
     if dist.is_initialized() and "RANK" in os.environ and backend is None:   # launched by torch.distributed.run: leave the group cleanly
         dist.destroy_process_group()
-    return {"frames": n, "shard": (a, b), "done": done, "seconds": dt, "output": out_path, "rank": rank, "world_size": ws}
+    return {"frames": n, "shard": (a, b), "done": done, "seconds": dt, "output": out_path, "rank": rank, "world_size": ws,
+            "parsing_dtype": None if par is None else par.compute_dtype}
 
 
 def _cpu_loop(opt, model, par, s_w, d_s, source, emit, first_index, bgr):

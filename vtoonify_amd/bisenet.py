@@ -142,7 +142,7 @@ class BiSeNet(nn.Module):
 class BiSeNetEngine:
     def __init__(self, state_dict: Dict[str, torch.Tensor], n_classes: int = 19,
                  dtype: torch.dtype = torch.bfloat16, device: Optional[torch.device] = None):
-        assert dtype in (torch.bfloat16, torch.float32)
+        assert dtype in (torch.bfloat16, torch.float16, torch.float32)
         self.dtype, self.dt = dtype, K.dt_code(dtype)
         self.device = device or next(iter(state_dict.values())).device
         if self.device.type != "cuda" and not _lib.is_emulation():

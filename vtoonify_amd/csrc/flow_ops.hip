@@ -248,6 +248,9 @@ extern "C" int vt_eltwise2(void* out, int ld_out, const void* a, int ld_a, const
     } else if (dtype == VT_BF16) {
         auto k = eltwise2_kernel<bf16_t>;
         VT_LAUNCH(k, dim3((unsigned)blocks), dim3(256), stream, (bf16_t*)out, ld_out, (const bf16_t*)a, ld_a, (const bf16_t*)b, ld_b, rows, c, op);
+    } else if (dtype == VT_F16) {
+        auto k = eltwise2_kernel<f16_t>;
+        VT_LAUNCH(k, dim3((unsigned)blocks), dim3(256), stream, (f16_t*)out, ld_out, (const f16_t*)a, ld_a, (const f16_t*)b, ld_b, rows, c, op);
     } else {
         vt_set_error("vt_eltwise2: dtype");
         return VT_ERR_UNSUPPORTED;
@@ -267,6 +270,9 @@ extern "C" int vt_gru_blend(void* h, int ld_h, const void* z, const void* q, int
     } else if (dtype == VT_BF16) {
         auto k = gru_blend_kernel<bf16_t>;
         VT_LAUNCH(k, dim3((unsigned)blocks), dim3(256), stream, (bf16_t*)h, ld_h, (const bf16_t*)z, (const bf16_t*)q, rows, c);
+    } else if (dtype == VT_F16) {
+        auto k = gru_blend_kernel<f16_t>;
+        VT_LAUNCH(k, dim3((unsigned)blocks), dim3(256), stream, (f16_t*)h, ld_h, (const f16_t*)z, (const f16_t*)q, rows, c);
     } else {
         vt_set_error("vt_gru_blend: dtype");
         return VT_ERR_UNSUPPORTED;

@@ -927,16 +927,19 @@ extern "C" int vt_channel_mean(float* mean, const void* x, int ld_x, int n, int 
                                int dtype, vt_stream stream) {
     VT_REQUIRE(mean && x && partials, "vt_channel_mean: null tensor");
     VT_REQUIRE(n > 0 && hw > 0 && c > 0 && c % 8 == 0, "vt_channel_mean: c must be a positive multiple of 8");
-    VT_REQUIRE(dtype == VT_F32 || dtype == VT_BF16, "vt_channel_mean: dtype");
+    VT_REQUIRE(dtype == VT_F32 || dtype == VT_BF16 || dtype == VT_F16, "vt_channel_mean: dtype");
     const int cpx = stat_chunk_pixels(hw);
     const int chunks = (hw + cpx - 1) / cpx;
     dim3 grid((unsigned)(n * chunks)), block(256);
     if (dtype == VT_F32) {
         auto k = instnorm_partial_kernel<float, false>;
         VT_LAUNCH(k, grid, block, stream, (StatRec*)partials, (const float*)x, ld_x, (const float*)nullptr, 0, hw, c, cpx, chunks);
-    } else {
+    } else if (dtype == VT_BF16) {
         auto k = instnorm_partial_kernel<bf16_t, false>;
         VT_LAUNCH(k, grid, block, stream, (StatRec*)partials, (const bf16_t*)x, ld_x, (const bf16_t*)nullptr, 0, hw, c, cpx, chunks);
+    } else {
+        auto k = instnorm_partial_kernel<f16_t, false>;
+        VT_LAUNCH(k, grid, block, stream, (StatRec*)partials, (const f16_t*)x, ld_x, (const f16_t*)nullptr, 0, hw, c, cpx, chunks);
     }
     int rc = vt_check_launch("vt_channel_mean(partial)");
     if (rc) return rc;
@@ -959,6 +962,10 @@ extern "C" int vt_se_apply(void* out, const void* res, const float* gate, const 
         auto k = se_apply_kernel<bf16_t>;
         VT_LAUNCH(k, dim3(grid_for((int64_t)n * oh * ow * (c / 8))), dim3(256), stream, (bf16_t*)out,
                   (const bf16_t*)res, gate, (const bf16_t*)shortcut, n, oh, ow, c, sc_h, sc_w, sc_stride);
+    } else if (dtype == VT_F16) {
+        auto k = se_apply_kernel<f16_t>;
+        VT_LAUNCH(k, dim3(grid_for((int64_t)n * oh * ow * (c / 8))), dim3(256), stream, (f16_t*)out,
+                  (const f16_t*)res, gate, (const f16_t*)shortcut, n, oh, ow, c, sc_h, sc_w, sc_stride);
     } else {
         vt_set_error("vt_se_apply: dtype");
         return VT_ERR_UNSUPPORTED;
@@ -978,6 +985,10 @@ extern "C" int vt_upsample_bilinear_add(void* out, const void* x, const void* y,
         auto k = upsample_add_kernel<bf16_t>;
         VT_LAUNCH(k, dim3(grid_for((int64_t)n * H * W * (c / 8))), dim3(256), stream, (bf16_t*)out, (const bf16_t*)x,
                   (const bf16_t*)y, n, h, w, H, W, c);
+    } else if (dtype == VT_F16) {
+        auto k = upsample_add_kernel<f16_t>;
+        VT_LAUNCH(k, dim3(grid_for((int64_t)n * H * W * (c / 8))), dim3(256), stream, (f16_t*)out, (const f16_t*)x,
+                  (const f16_t*)y, n, h, w, H, W, c);
     } else {
         vt_set_error("vt_upsample_bilinear_add: dtype");
         return VT_ERR_UNSUPPORTED;

@@ -163,6 +163,10 @@ extern "C" int vt_maxpool2d(void* out, const void* x, int n, int h, int w, int c
         auto kfn = maxpool_kernel<bf16_t>;
         VT_LAUNCH(kfn, dim3(pg_grid((int64_t)n * oh * ow * (c / 8))), dim3(256), stream, (bf16_t*)out,
                   (const bf16_t*)x, n, h, w, c, oh, ow, k, stride, pad);
+    } else if (dtype == VT_F16) {
+        auto kfn = maxpool_kernel<f16_t>;
+        VT_LAUNCH(kfn, dim3(pg_grid((int64_t)n * oh * ow * (c / 8))), dim3(256), stream, (f16_t*)out,
+                  (const f16_t*)x, n, h, w, c, oh, ow, k, stride, pad);
     } else {
         vt_set_error("vt_maxpool2d: dtype");
         return VT_ERR_UNSUPPORTED;
@@ -184,6 +188,10 @@ extern "C" int vt_gate_add_nearest(void* out, const void* res, const float* gate
         auto kfn = gate_add_nearest_kernel<bf16_t>;
         VT_LAUNCH(kfn, dim3(pg_grid((int64_t)n * out_h * out_w * (c / 8))), dim3(256), stream, (bf16_t*)out,
                   (const bf16_t*)res, gate, add_vec, (const bf16_t*)add, n, h, w, c, out_h, out_w);
+    } else if (dtype == VT_F16) {
+        auto kfn = gate_add_nearest_kernel<f16_t>;
+        VT_LAUNCH(kfn, dim3(pg_grid((int64_t)n * out_h * out_w * (c / 8))), dim3(256), stream, (f16_t*)out,
+                  (const f16_t*)res, gate, add_vec, (const f16_t*)add, n, h, w, c, out_h, out_w);
     } else {
         vt_set_error("vt_gate_add_nearest: dtype");
         return VT_ERR_UNSUPPORTED;
@@ -219,6 +227,10 @@ extern "C" int vt_resize_bilinear(void* out, int out_layout, int ld_out, int out
     } else if (out_dtype == VT_BF16) {
         auto kfn = resize_bilinear_kernel<bf16_t>;
         VT_LAUNCH(kfn, dim3(pg_grid(total)), dim3(256), stream, (bf16_t*)out, nhwc, ld_out, in, n, c, h, w, sy, sx,
+                  align_corners ? 1 : 0, step, out_h, out_w, mul);
+    } else if (out_dtype == VT_F16) {
+        auto kfn = resize_bilinear_kernel<f16_t>;
+        VT_LAUNCH(kfn, dim3(pg_grid(total)), dim3(256), stream, (f16_t*)out, nhwc, ld_out, in, n, c, h, w, sy, sx,
                   align_corners ? 1 : 0, step, out_h, out_w, mul);
     } else {
         vt_set_error("vt_resize_bilinear: out dtype");

@@ -139,9 +139,9 @@ class GradualStyleEncoder(nn.Module):
 class PspEngine:
     def __init__(self, state_dict: Dict[str, torch.Tensor], n_styles: int = 18,
                  dtype: torch.dtype = torch.bfloat16, device: Optional[torch.device] = None):
-        assert dtype in (torch.bfloat16, torch.float32)
+        assert dtype in (torch.bfloat16, torch.float16, torch.float32)
         self.dtype, self.dt = dtype, K.dt_code(dtype)
-        self.esz = 2 if dtype == torch.bfloat16 else 4
+        self.esz = torch.empty((), dtype=dtype).element_size()
         self.device = device or next(iter(state_dict.values())).device
         if self.device.type != "cuda" and not _lib.is_emulation():
             raise _lib.VtError("PspEngine needs a GPU device (no CPU path)")

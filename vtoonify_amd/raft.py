@@ -127,15 +127,20 @@ def _register(root: nn.Module, key: str, shape):
 
 
 class RAFT(nn.Module):
-    """model.raft.core.raft.RAFT(args) -- args.small / mixed_precision / alternate_corr are accepted; only the
-    configuration the reference builds (not small) exists here."""
+    """model.raft.core.raft.RAFT(args) -- args.small / alternate_corr are accepted; only the configuration the
+    reference builds (not small) exists here.  compute_dtype: an explicit dtype wins; with None,
+    args.mixed_precision=True selects fp16 (the reference's meaning of the flag: fp16 autocast of the two encoders and
+    the update block, raft.py:99-137) and anything else fp32.  The correlation pyramid and lookup, coords, flow and the
+    convex up-sampling are fp32 in every form."""
 
-    def __init__(self, args=None, compute_dtype=torch.float32):
+    def __init__(self, args=None, compute_dtype=None):
         super().__init__()
         if args is not None and getattr(args, "small", False):
             raise _lib.VtError("RAFT: the small model is not built (smooth_parsing_map.py uses the full one)")
         self.args = args
         self.hidden_dim, self.context_dim = 128, 128
+        if compute_dtype is None:
+            compute_dtype = torch.float16 if bool(getattr(args, "mixed_precision", False)) else torch.float32
         self.compute_dtype = compute_dtype
         for key, shape in raft_schema().items():
             _register(self, key, shape)
@@ -197,12 +202,15 @@ class RaftEngine:
             self.device = torch.device("cuda", torch.cuda.current_device())
         if self.device.type != "cuda" and not _lib.is_emulation():
             raise _lib.VtError("RaftEngine needs a GPU device (no CPU path)")
+        if dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise _lib.VtError(f"RaftEngine: dtype {dtype} (float32, bfloat16 or float16)")
         self.dtype, self.dt = dtype, K.dt_code(dtype)
-        self.esz = 4 if dtype == torch.float32 else 2
+        self.esz = torch.empty((), dtype=dtype).element_size()
         f32 = lambda k: sd[k].to(self.device, torch.float32)
         self.w: Dict[str, torch.Tensor] = {}
         self.b: Dict[str, torch.Tensor] = {}
         self.keep_taps = False      # tests: keep intermediate tensors of the first iteration in self.taps
+        self.keep_bufs = None       # tests: a list collects every activation buffer of a pass (the range check)
         self._graphs = {}           # (shape, iters) -> "seen" | (hipGraph, static inputs, outputs)
 
         def add(name, key, bn=None, cin_dst=None, chan_map=None, rows=None):
@@ -250,7 +258,10 @@ class RaftEngine:
     # ------------------------------------------------------------------ helpers
     def _buf(self, shape, dtype=None, zero=False):
         f = torch.zeros if zero else torch.empty
-        return f(shape, dtype=dtype or self.dtype, device=self.device)
+        t = f(shape, dtype=dtype or self.dtype, device=self.device)
+        if self.keep_bufs is not None:
+            self.keep_bufs.append(t)
+        return t
 
     def _conv(self, name, src0, c0, ld0, n, h, w, cout, kh, kw, out, ld_out, stride=1, pad=0, pad_w=None, act=ACT_NONE,
               slope=0.0, gain=1.0, src1=None, c1=0, ld1=0, resid=None, ld_res=0, beta=0.0, post_relu=0, planar=False):
@@ -275,7 +286,7 @@ class RaftEngine:
         sc, sh = self._buf((n, c), torch.float32), self._buf((n, c), torch.float32)
         ws = self._buf((max(K.instnorm_ws_bytes(n, hw, c), 16),), torch.uint8)
         K.instnorm_stats(sc, sh, x, c, n, hw, c, ws, self.dt, stream_of=x)
-        y = torch.empty_like(x)
+        y = self._buf(x.shape, x.dtype)
         K.affine_apply(y, c, x, c, sc, sh, n, hw, c, self.dt, stream_of=x)
         return self._relu_(y)
 
@@ -304,7 +315,7 @@ class RaftEngine:
                         sc, sh = self._buf((n, dim), torch.float32), self._buf((n, dim), torch.float32)
                         ws = self._buf((max(K.instnorm_ws_bytes(n, oh * ow, dim), 16),), torch.uint8)
                         K.instnorm_stats(sc, sh, short, dim, n, oh * ow, dim, ws, self.dt, stream_of=short)
-                        s2 = torch.empty_like(short)
+                        s2 = self._buf(short.shape, short.dtype)
                         K.affine_apply(s2, dim, short, dim, sc, sh, n, oh * ow, dim, self.dt, stream_of=short)
                         short = s2
                 y2 = self._buf((n, oh, ow, dim))
@@ -529,7 +540,7 @@ class RaftEngine:
     def _fmap_out(self, fmap):
         if self.dtype == torch.float32:
             return fmap
-        self._fmap_lo = torch.empty(fmap.shape, dtype=self.dtype, device=self.device)
+        self._fmap_lo = self._buf(fmap.shape)
         return self._fmap_lo
 
     def _fmap_done(self, fmap):

@@ -151,7 +151,8 @@ class ParsingSmoother:
     one vt_parsing_fuse, the Downsample.  Window slots that alias a frame at the clip's ends share its cached features.
 
     Device memory is bounded by the window, not the clip.  With S = 2H * 2W, s = S / 64 and e = bytes of RAFT's
-    compute type, a ring slot holds
+    compute type (4 in fp32, 2 in bf16 and fp16: the GRU input rows; the feature pyramid is fp32 in every mode), a
+    ring slot holds
         Is 12 S  +  Ps 76 S  +  RAFT features (1024 * 85/64 + 400 e) s          bytes,
     at most 2w+1 slots are alive (`peak_slots`), and fusing a window stages (2w+1) * 96 S bytes (frames, maps, flows)
     next to the transient activations of one BiSeNet pass and one refine of 2w pairs:
