@@ -496,4 +496,6 @@ int vt_mfma_selftest(float* c, const void* a, const void* b, int dtype, vt_strea
 #include "vtoonify_amd_rgbup.h"
 /* ... and the face alignment for the style encoder from given landmarks. */
 #include "vtoonify_amd_align.h"
+/* ... and the noise and latent arithmetic of the StyleGAN2 / DualStyleGAN generator forward. */
+#include "vtoonify_amd_generator.h"
 #endif /* VTOONIFY_AMD_H */

@@ -185,6 +185,18 @@ _ALIGN_SIGS = {
 }
 ALIGN_SYMBOLS = tuple(_ALIGN_SIGS)
 
+# include/vtoonify_amd_generator.h: noise and latent arithmetic of the StyleGAN2 / DualStyleGAN generator forward, additive to
+# ABI version 5
+_GENERATOR_SIGS = {
+    "vt_philox_u32": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "vt_randn": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "vt_noise_bias_act": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vt_lerp_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                               C.c_int, C.c_void_p]),
+}
+GENERATOR_SYMBOLS = tuple(_GENERATOR_SIGS)
+
 _lib = None
 _lib_path = None
 
@@ -197,7 +209,7 @@ def _bind(path: str):
     import torch  # noqa: F401
     lib = C.CDLL(path)
     for name, (res, args) in {**_SIGS, **_PREPASS_SIGS, **_FRAMES_SIGS, **_FUSION_SIGS, **_RGBUP_SIGS,
-                              **_ALIGN_SIGS}.items():
+                              **_ALIGN_SIGS, **_GENERATOR_SIGS}.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args

@@ -4,7 +4,8 @@
 The module tree below only HOLDS parameters under the reference's names (399 state_dict
 entries for backbone='dualstylegan', 229 for 'toonify') so that
 `VToonify(backbone).load_state_dict(ckpt['g_ema'])` (style_transfer.py:62-64) works
-unchanged.  With the parameters on a GPU all arithmetic happens in the HIP engine and nothing
+unchanged; `generator` / `stylegan()` additionally carry their own forward (generator.py), which
+VToonify.forward never calls.  With the parameters on a GPU all arithmetic happens in the HIP engine and nothing
 falls back; with the parameters on the CPU (`style_transfer.py --cpu`, :32,55) the forward
 pass is the reference's eager operator sequence over the CPU-tensor branch of the operator
 surface (eager.py, op/native.py) -- the reference's own "CPU tensors -> native path" contract.
@@ -127,12 +128,13 @@ def _ada_res(c, style_dim=512):
 
 
 class _DualStyleGAN(nn.Module):
-    """Parameter layout of DualStyleGAN (model/dualstylegan.py:47-82)."""
+    """Parameter layout of DualStyleGAN (model/dualstylegan.py:47-82); generator.py's DualStyleGAN adds the forward."""
+    _stylegan_cls = _StyleGAN2
 
     def __init__(self, size, style_dim, n_mlp, mult, res_index=6):
         super().__init__()
         self.style = _mapping(n_mlp - 6)
-        self.generator = _StyleGAN2(size, style_dim, n_mlp, mult)
+        self.generator = self._stylegan_cls(size, style_dim, n_mlp, mult)
         self.res = nn.ModuleList([_ada_res(self.generator.channels[4])])
         res_index = res_index // 2 * 2
         for i in range(3, self.generator.log_size + 1):
@@ -206,10 +208,15 @@ class VToonify(nn.Module):
         self.in_size = in_size
         self.style_channels = style_channels
         self.compute_dtype = compute_dtype
+        # the generators carry their own forward (generator.py: portrait stylisation, style-image and paired-data synthesis)
+        # in this module's precision; VToonify.forward below never calls it
+        from .generator import DualStyleGAN, Generator
         if backbone == "dualstylegan":
-            self.generator = _DualStyleGAN(out_size, style_channels, num_mlps, channel_multiplier)
+            self.generator = DualStyleGAN(out_size, style_channels, num_mlps, channel_multiplier)
         else:
-            self.generator = _StyleGAN2(out_size, style_channels, num_mlps, channel_multiplier)
+            self.generator = Generator(out_size, style_channels, num_mlps, channel_multiplier)
+        for m in (self.generator, self.stylegan()):
+            m.compute_dtype, m.exact_fp32 = compute_dtype, self.exact_fp32
         ch = self.generator.channels
         enc_res = [2 ** i for i in range(int(math.log2(in_size)), 4, -1)]
         self.encoder = nn.ModuleList([nn.Sequential(
