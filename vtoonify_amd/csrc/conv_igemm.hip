@@ -208,6 +208,24 @@ struct Mma<f32x3_t> {   // on already split operands: (weights head, weights rem
         Mma<bf16_t>::run(acc, wh, al);
         Mma<bf16_t>::run(acc, wl, ah);
     }
+    // The form of the kernels that keep ALL of K in one accumulator (mma_row: the 1-D direct-to-LDS and the patch tiles): the
+    // three products of a 32-channel row are summed from ZERO and the row's sum is added to `acc` once.  Chained on `acc` itself
+    // every MFMA rounds against the running sum of the whole K range -- the matrix core rounds as it adds, several times per
+    // instruction -- and the two remainder products (2^-9 of the row) each cost as much as the full one: the worst
+    // |y - model| was 2.2 .. 3.0 x 2^-24 S per element on these kernels, five times the whole-K kernel's (eight waves, then
+    // LDS; it and conv_upblur keep run3) and above four times a float32 evaluation of the same model on two cases
+    // (tests/test_conv_f32x3.py, profiles/f32x3_kernels.txt).  Here a row rounds against its own 32 products and `acc` is
+    // rounded once per row, at four vector additions per three MFMAs.
+    static __device__ __forceinline__ void run3_row(f32x4& acc, const u128& wh, const u128& wl, const u128& ah, const u128& al) {
+        f32x4 row = f32x4{0.f, 0.f, 0.f, 0.f};
+        Mma<bf16_t>::run(row, wl, ah);
+        Mma<bf16_t>::run(row, wh, al);
+        Mma<bf16_t>::run(row, wh, ah);
+        acc[0] += row[0];
+        acc[1] += row[1];
+        acc[2] += row[2];
+        acc[3] += row[3];
+    }
 };
 template <typename T>
 struct is_bf16 {
@@ -248,7 +266,7 @@ __device__ __forceinline__ void mma_row(f32x4 (&acc)[TM][TN], PA&& pa, PB&& pb) 
 #pragma unroll
         for (int a = 0; a < TM; ++a)
 #pragma unroll
-            for (int b = 0; b < TN; ++b) Mma<f32x3_t>::run3(acc[a][b], bh[b], bl[b], ah[a], al[a]);
+            for (int b = 0; b < TN; ++b) Mma<f32x3_t>::run3_row(acc[a][b], bh[b], bl[b], ah[a], al[a]);
     } else {
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
